@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native kcount stage (BASELINE.json metric: k-mers/s, whole node, k=21, 150 bp).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: either under python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...,
    or plain: bench.py then starts the N ranks itself as child processes, before it touches the GPU)
   python bench.py --gpus N --transport host ...   N ranks exchanging through the host-staged transport
@@ -17,11 +17,20 @@ Workloads (--config):
   C4: configs[3] — C3 at k = 63.
 value = counted k-mer occurrences of all ranks / max-over-ranks time.
 
-Extra JSON fields: roofline (dominant kernel: algorithmic HBM bytes per launch over its HIP-event time against
-8 TB/s; k_count also carries its LDS-floor model), cpu_baseline (the multi-threaded CPU restatement on a bounded
-sample, rank 0 at N = 1), stages (per-stage device ms per step), h2d_inclusive (BASELINE.md's window: the same step
-from reads in pinned host memory, timed from the first H2D, median of 5 after 3 warm-ups), d2h_fetch (copying the
-finished table to the host), kmermap (the streamed hand-off into the C++ adapter's KmerMap).
+A plain run sets up, warms up, times the K steps and prints the line: value, ms_per_step (wall time of the timed
+region / K) and what the steps' own stage events give without further runs: stages (per-stage device ms per step)
+and roofline (dominant kernel: algorithmic HBM bytes per launch over its HIP-event time against 8 TB/s; k_count also
+carries its LDS-floor model).
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed (the finished table a caller would
+fetch) goes to DIR/<name>.npy (dump_outputs below; <name>_rank<r>.npy for ranks r > 0). The inputs depend on the
+arguments only, so two builds run with the same arguments can be compared file by file.
+
+--full adds the legs that take runs of their own (null in a plain run's line): cpu_baseline (the multi-threaded CPU
+restatement on a bounded sample, rank 0 at N = 1), h2d_inclusive (BASELINE.md's window: the same step from reads in
+pinned host memory, timed from the first H2D, median of 5 after 3 warm-ups), d2h_fetch (copying the finished table
+to the host), kmermap (the streamed hand-off into the C++ adapter's KmerMap), k63 (N = 1, C2: the same reads at
+k = 63). --cpu-*, --no-cpu-baseline, --h2d-steps, --no-k63 and --no-kmermap choose among them under --full.
 """
 from __future__ import annotations
 
@@ -52,6 +61,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: CPU baseline, H2D-inclusive window, D2H fetch, "
+                         "KmerMap hand-off, the k = 63 leg (each can still be switched off by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the finished table) as DIR/<name>.npy")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="C2")
     ap.add_argument("--k", type=int, default=None, help="override the config's k")
     ap.add_argument("--reads-per-gpu", type=int, default=None, help="override (C2: reads per GPU)")
@@ -90,7 +104,10 @@ def parse():
                          "§3.5b; k <= 31: record exchange + hand-off)")
     ap.add_argument("--pmc-json", default=str(ROOT / "profiles" / "pmc_traffic.json"),
                     help="per-kernel HBM bytes per launch from rocprofv3 --pmc passes (profiles/), if present")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline's steps only
+        args.no_cpu_baseline, args.h2d_steps, args.k63, args.kmermap = True, 0, False, False
+    return args
 
 
 def algorithmic_bytes(stage: str, st: dict, k: int) -> float:
@@ -251,6 +268,56 @@ def cpu_baseline(b, o, k, n_reads, threads):
     return {"value": occ / dt, "unit": "k-mers/s", "cores": threads, "kind": "port",
             "sample": f"first {n} reads of this rank's shard ({occ} k-mers), oracle/kcount_mt.c, {threads} threads, "
                       f"{dt:.1f} s"}
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of the sampled rows (the files stay under 64 MB in all)
+DUMP_SEED = 0x6B636F756E743031
+
+
+def dump_outputs(counter, st: dict, out_dir, rank: int = 0) -> dict:
+    """--dump-outputs: the finished table of the last timed step, as a caller receives it from fetch(), in .npy files
+    that two builds can be compared by. The table's row order is not part of the result (it follows the order in
+    which blocks finish), and C2's 52M rows are 0.6 GB, so the files hold
+      totals.npy  float64 [n_out, distinct, occurrences, count_sum, sum of counts, sum of left, sum of right,
+                  then per key word its sum mod 2^48] over every row of the table (all exact in float64);
+      keys.npy    float64 [m, 2 * n_longs]: per key word its high and low 32 bits, of a fixed sample of the rows
+                  in Kmer::operator< order; counts.npy, left.npy, right.npy: float32 [m] of the same rows.
+    The sample is every row whose seeded hash of the key has its top s bits zero; s depends on the input alone
+    (occurrences, key width), so the same rows are chosen whatever order the table came in."""
+    import numpy as np
+
+    t = counter.fetch()
+    nl = t.keys.shape[1]
+    row_bytes = 16 * nl + 12
+    s = 0
+    while (st["occurrences"] >> s) * row_bytes > DUMP_BUDGET_BYTES:
+        s += 1
+    h = np.full(len(t), 0x9E3779B97F4A7C15 ^ DUMP_SEED, dtype=np.uint64)
+    for w in range(nl):
+        h = (h ^ t.keys[:, w]) * np.uint64(0xBF58476D1CE4E5B9)
+        h ^= h >> np.uint64(31)
+    h *= np.uint64(0x94D049BB133111EB)
+    sel = np.flatnonzero((h >> np.uint64(64 - s)) == 0) if s else np.arange(len(t))
+    del h
+    if sel.size * row_bytes > (60 << 20):  # n_out <= occurrences, so only a hash far from uniform gets here
+        raise SystemExit(f"bench.py: --dump-outputs sample of {sel.size} rows is over the size limit")
+    sample = type(t)(t.k, t.keys[sel], t.counts[sel], t.left[sel], t.right[sel]).sorted()
+    key_sums = [int(t.keys[:, w].sum(dtype=np.uint64)) & ((1 << 48) - 1) for w in range(nl)]
+    totals = np.array([st["n_out"], st["distinct"], st["occurrences"], st["count_sum"],
+                       int(t.counts.sum(dtype=np.uint64)), int(t.left.sum(dtype=np.uint64)),
+                       int(t.right.sum(dtype=np.uint64)), *key_sums], dtype=np.float64)
+    halves = np.empty((len(sample), 2 * nl), dtype=np.float64)
+    halves[:, 0::2] = sample.keys >> np.uint64(32)
+    halves[:, 1::2] = sample.keys & np.uint64(0xFFFFFFFF)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    files = {"totals": totals, "keys": halves, "counts": sample.counts.astype(np.float32),
+             "left": sample.left.astype(np.float32), "right": sample.right.astype(np.float32)}
+    for name, a in files.items():
+        np.save(out_dir / f"{name}{sfx}.npy", a)
+    return {"dir": str(out_dir), "rows": int(len(t)), "sample_rows": int(len(sample)), "sample_shift": s,
+            "bytes": int(sum(a.nbytes for a in files.values()))}
 
 
 def launch_ranks(n: int) -> int:
@@ -438,6 +505,12 @@ def main():
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
         occ_total = int(c.item())
 
+    dumped = None
+    if args.dump_outputs:  # every rank its own rows
+        if counter.n_out is None:
+            raise SystemExit("bench.py: --dump-outputs needs at least one step (timed or warm-up)")
+        dumped = dump_outputs(counter, st or counter.stats(), args.dump_outputs, rank)
+
     value = occ_total / elapsed
     steps = max(1, args.steps)
     per_step = {s_: v / steps for s_, v in stage_ms.items()}
@@ -496,28 +569,30 @@ def main():
 
     # the hand-off into the adapter's KmerMap first: its first run includes the device sort into slot order
     kmermap = handoff_ms(counter, k, threads) if rank == 0 and args.kmermap else None
-    n_rows = counter.n_out
-    row_b = 8 * counter.n_longs + 4
-    table = m.KmerTable(k, np.ones((n_rows, counter.n_longs), np.uint64), np.ones(n_rows, np.uint16),
-                        np.ones(n_rows, np.uint8), np.ones(n_rows, np.uint8))
-    d2h_ms = timed_fetch(False, table)
-    d2h = {"ms": round(d2h_ms, 2), "rows": n_rows, "bytes": int(n_rows * row_b),
-           "GBps": round(n_rows * row_b / (d2h_ms * 1e-3) / 1e9, 2) if d2h_ms else None,
-           "ordered_ms": round(timed_fetch(True, table), 2),
-           "into": "existing pageable host arrays (numpy)"}
-    try:
-        pin = [torch.empty(a.shape, dtype=t, pin_memory=True) for a, t in
-               ((table.keys, torch.int64), (table.counts, torch.int16), (table.left, torch.uint8),
-                (table.right, torch.uint8))]
-        ptab = m.KmerTable(k, pin[0].numpy().view(np.uint64), pin[1].numpy().view(np.uint16), pin[2].numpy(),
-                           pin[3].numpy())
-        d2h["pinned_ms"] = round(timed_fetch(False, ptab), 2)
-        d2h["pinned_ordered_ms"] = round(timed_fetch(True, ptab), 2)
-        d2h["pinned_GBps"] = round(n_rows * row_b / (d2h["pinned_ms"] * 1e-3) / 1e9, 2)
-        del ptab, pin
-    except RuntimeError:
-        pass
-    del table
+    d2h = None
+    if args.full:
+        n_rows = counter.n_out
+        row_b = 8 * counter.n_longs + 4
+        table = m.KmerTable(k, np.ones((n_rows, counter.n_longs), np.uint64), np.ones(n_rows, np.uint16),
+                            np.ones(n_rows, np.uint8), np.ones(n_rows, np.uint8))
+        d2h_ms = timed_fetch(False, table)
+        d2h = {"ms": round(d2h_ms, 2), "rows": n_rows, "bytes": int(n_rows * row_b),
+               "GBps": round(n_rows * row_b / (d2h_ms * 1e-3) / 1e9, 2) if d2h_ms else None,
+               "ordered_ms": round(timed_fetch(True, table), 2),
+               "into": "existing pageable host arrays (numpy)"}
+        try:
+            pin = [torch.empty(a.shape, dtype=t, pin_memory=True) for a, t in
+                   ((table.keys, torch.int64), (table.counts, torch.int16), (table.left, torch.uint8),
+                    (table.right, torch.uint8))]
+            ptab = m.KmerTable(k, pin[0].numpy().view(np.uint64), pin[1].numpy().view(np.uint16), pin[2].numpy(),
+                               pin[3].numpy())
+            d2h["pinned_ms"] = round(timed_fetch(False, ptab), 2)
+            d2h["pinned_ordered_ms"] = round(timed_fetch(True, ptab), 2)
+            d2h["pinned_GBps"] = round(n_rows * row_b / (d2h["pinned_ms"] * 1e-3) / 1e9, 2)
+            del ptab, pin
+        except RuntimeError:
+            pass
+        del table
 
     # the same step from reads in pinned host memory: chunked H2D on a copy stream, each chunk extracted as
     # soon as it lands (mhmkc_add_reads); the timed region starts at the first H2D
@@ -686,6 +761,8 @@ def main():
                           "GBps_rank0": round(st["bytes_sent"] / (per_step["exchange"] * 1e-3) / 1e9, 2)
                           if per_step.get("exchange") else None}
                          if world > 1 and st else None),
+            "full": args.full,
+            "dumped_outputs": dumped,
             "synth_seconds": round(gen_s, 2),
             "build_id": m._native.build_id(),
             "build_id_matches_tree": m._native.build_id() == source_build_id(),

@@ -9,7 +9,8 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 step() { echo "[$(date +%T)] $*"; }
 step bench
-timeout -k 10 400 python3 -u bench.py > gpurun_out/${P}_bench.json 2> gpurun_out/${P}_bench.err || { echo "bench failed"; tail -5 gpurun_out/${P}_bench.err; exit 1; }
+BENCH_OUT=${BENCH_OUT:-${P}_bench}  # the whole bench line (--full) goes to $BENCH_OUT.json, its stderr to $BENCH_OUT.err
+timeout -k 10 400 python3 -u bench.py --full > $BENCH_OUT.json 2> $BENCH_OUT.err || { echo "bench failed"; tail -5 $BENCH_OUT.err; exit 1; }
 step kstats k21
 bash tools/gpu_kstats.sh ${P}_kstats_k21 --steps 5 --warmup 2 --no-cpu-baseline --h2d-steps 0 --no-kmermap --no-k63 || exit 1
 step kstats k63
