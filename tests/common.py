@@ -107,6 +107,33 @@ def ctg_set(seed: int = 21, n_reads: int = 300, genome_len: int = 6000, n_ctgs: 
     return b, o, seqs, np.array(depths, dtype=np.uint16)
 
 
+def long_ragged_set(k: int, seed: int = 61):
+    """Reads of every awkward length for the valid-window list of the two-word extraction: empty, < k + 2,
+    k + 2 (one window), k + 3, 150, and reads far longer than a 2048-base tile (a read spanning several
+    tiles, starting before the tile it is counted in), concatenated in a random order."""
+    rng = np.random.default_rng(seed)
+    g = m.synth_genome(400_000, seed)
+    lens = [0, 1, k, k + 1, k + 2, k + 3, 150, 151, 2047, 2048, 2049, 4000, 9000]
+    reads = []
+    for i in range(600):
+        L = lens[i % len(lens)] if i % 3 else int(rng.integers(0, 300))
+        a = int(rng.integers(0, g.size - L - 1))
+        q = np.where(rng.random(L) < 0.03, 5, 31).astype(np.uint8)
+        reads.append((g[a:a + L] & 7) | (q << 3))
+    rng.shuffle(reads)
+    offs = np.zeros(len(reads) + 1, dtype=np.uint64)
+    np.cumsum([r.size for r in reads], out=offs[1:])
+    return np.concatenate(reads).astype(np.uint8), offs
+
+
+def ref_table(b, o, k, seqs=(), depths=(), **kw) -> m.KmerTable:
+    """The table of the reference's own analyze_kmers (oracle/_ref/libkcountref.so, built by `make -C oracle` where
+    the reference tree is present); the run must have raised no warning and dropped no insert."""
+    t = O.ref_analyze_kmers(b, o, k, seqs, depths, **kw)
+    assert (t.warnings, t.dropped) == (0, 0), f"reference build: {t.warnings} warnings, {t.dropped} dropped inserts"
+    return m.KmerTable(k, t.keys, t.counts, t.left, t.right)
+
+
 def oracle_ctg_table(b, o, seqs, depths, k, **kw) -> m.KmerTable:
     t = O.kcount_ctgs(b, o, seqs, depths, k, **kw)
     keys, c, l, r = t.fetch()
@@ -195,6 +222,25 @@ def read_reads_file(path: Path):
     offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
     np.cumsum(lens, out=offs[1:])
     return (np.concatenate(seqs) if seqs else np.zeros(0, np.uint8)).astype(np.uint8), offs
+
+
+def read_ctgs_file(path: Path):
+    """'seq depth' lines (contigs in the order they are applied; lowercase = below the quality cutoff) -> (seqs, depths)."""
+    seqs, depths = [], []
+    with gzip.open(path, "rt") as f:
+        for line in f:
+            s, d = line.split()
+            seqs.append(s)
+            depths.append(int(d))
+    return seqs, np.array(depths, dtype=np.uint16)
+
+
+def golden_input(setname: str):
+    """A golden set's reads and, where it has a ctgs_<set>.txt.gz, its contigs: (bytes, offsets, seqs, depths)."""
+    b, o = read_reads_file(GOLDEN / f"reads_{setname}.txt.gz")
+    ctgs = GOLDEN / f"ctgs_{setname}.txt.gz"
+    seqs, depths = read_ctgs_file(ctgs) if ctgs.exists() else ([], np.zeros(0, np.uint16))
+    return b, o, seqs, depths
 
 
 def read_table_file(path: Path, k: int) -> m.KmerTable:

@@ -1,9 +1,11 @@
 """Regenerate the golden fixtures of tests/golden/ (run from the repo root: python tests/golden/make_golden.py).
 
 Inputs are 'seq qual' lines (BASELINE.md's input format; qualities in Phred+33, capped at Q31 as
-PackedRead stores them). Expected tables are produced by the CPU oracle (oracle/kcount_oracle.c, the
-restatement of the reference kcount read pass pinned as described in DESIGN.md §2) and written in the
-reference's dump_kmers line format "KMER count L R" (src/kcount/kmer_dht.cpp:243-266), sorted by k-mer.
+PackedRead stores them) and, for the contig set, 'seq depth' lines (contigs in the order they are applied; lowercase
+= a base below the quality cutoff). Expected tables are the output of the reference's own analyze_kmers, built
+single-rank from its unmodified sources (oracle/_ref/libkcountref.so: oracle/Makefile `ref`), written in
+the reference's dump_kmers line format "KMER count L R" (src/kcount/kmer_dht.cpp:243-266), sorted by k-mer. The script
+needs that build and stops without it: the fixtures are never the oracle's own output.
 """
 import gzip
 import sys
@@ -16,34 +18,60 @@ sys.path.insert(0, str(HERE.parents[1]))
 import numpy as np  # noqa: E402
 
 import mhm2_proxy_amd as m  # noqa: E402
-from common import edge_case_set, hot_set, oracle_table, synth_set  # noqa: E402
+import oracle_lib as O  # noqa: E402
+from common import ctg_set, edge_case_set, hot_set, ref_table, synth_set  # noqa: E402
 
+# name: (input maker -> (bytes, offsets, contig seqs, contig depths), k values)
 SETS = {
-    "s100": (lambda: synth_set(2000, 10000, 100), [21, 33, 55, 63, 77, 99]),
-    "edge": (lambda: edge_case_set(), [21, 33, 63]),
-    "hot": (lambda: hot_set(), [21]),
+    "s100": (lambda: synth_set(2000, 10000, 100) + ((), ()), [21, 33, 55, 63, 77, 99]),
+    "edge": (lambda: edge_case_set() + ((), ()), [21, 33, 63, 99]),
+    "hot": (lambda: hot_set() + ((), ()), [21]),
+    "ctg": (lambda: ctg_set(seed=61), [21, 33, 63, 99]),
 }
 
 
+def write_gz(path, lines) -> str:
+    """Writes the lines, unless the file already holds exactly them (a gzip header carries a time stamp, so a
+    rewritten file would differ in bytes with nothing changed); returns what was done."""
+    text = "".join(line + "\n" for line in lines).encode()
+    if path.exists():
+        with gzip.open(path, "rb") as f:
+            if f.read() == text:
+                return "unchanged"
+        what = "CHANGED"
+    else:
+        what = "new"
+    with open(path, "wb") as raw, gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=raw, mtime=0) as f:
+        f.write(text)
+    return what
+
+
 def write_reads(path, b, o):
-    with gzip.open(path, "wt", compresslevel=9) as f:
-        for i in range(o.size - 1):
-            r = b[int(o[i]):int(o[i + 1])]
-            seq = "".join("ACGTN"[x & 7] for x in r)
-            qual = "".join(chr(33 + (int(x) >> 3)) for x in r)
-            f.write(f"{seq} {qual}\n")
+    lines = []
+    for i in range(o.size - 1):
+        r = b[int(o[i]):int(o[i + 1])]
+        seq = "".join("ACGTN"[x & 7] for x in r)
+        qual = "".join(chr(33 + (int(x) >> 3)) for x in r)
+        lines.append(f"{seq} {qual}")
+    return write_gz(path, lines)
+
+
+def write_ctgs(path, seqs, depths):
+    return write_gz(path, [f"{s} {int(d)}" for s, d in zip(seqs, depths)])
 
 
 def main():
+    if O.kcountref() is None:
+        sys.exit(f"{O.KCOUNTREF[None]} is missing: the golden tables are the reference build's output "
+                 "(make -C oracle, with the reference tree present)")
     for name, (make, ks) in SETS.items():
-        b, o = make()
-        write_reads(HERE / f"reads_{name}.txt.gz", b, o)
+        b, o, seqs, depths = make()
+        print(name, "reads", write_reads(HERE / f"reads_{name}.txt.gz", b, o))
+        if len(seqs):
+            print(name, "contigs", write_ctgs(HERE / f"ctgs_{name}.txt.gz", seqs, depths))
         for k in ks:
-            t = oracle_table(b, o, k).sorted()
-            with gzip.open(HERE / f"table_{name}_k{k}.tsv.gz", "wt", compresslevel=9) as f:
-                for line in t.lines():
-                    f.write(line + "\n")
-            print(name, k, len(t))
+            t = ref_table(b, o, k, seqs, depths).sorted()
+            print(name, k, len(t), write_gz(HERE / f"table_{name}_k{k}.tsv.gz", t.lines()))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,9 @@
 """ctypes binding of oracle/liboracle.so — TEST INFRASTRUCTURE ONLY (the CPU checker).
 
-Also binds oracle/_ref/libhashref.so, the reference's own src/hash_funcs.c compiled unmodified
-(oracle/Makefile), when it has been built.
+Also binds, when they have been built (oracle/Makefile `ref`, only where the reference tree is present):
+oracle/_ref/libhashref.so, the reference's own src/hash_funcs.c compiled unmodified, and
+oracle/_ref/libkcountref.so (+ the _q25d75 build), the reference's own CPU kcount path compiled unmodified against
+one-rank stand-in headers, through the C ABI of oracle/ref_driver.cpp (kcountref, RefKmer, ref_analyze_kmers).
 """
 from __future__ import annotations
 
@@ -96,6 +98,163 @@ def hashref():
     L.quick_hash.argtypes = [C.c_uint64]
     L.quick_hash.restype = C.c_uint64
     return L
+
+
+KCOUNTREF = {None: ROOT / "oracle" / "_ref" / "libkcountref.so",
+             "q25d75": ROOT / "oracle" / "_ref" / "libkcountref_q25d75.so"}
+# what each build of the reference was compiled with (KCOUNT_QUAL_CUTOFF, DYN_MIN_DEPTH), oracle/Makefile
+KCOUNTREF_PARAMS = {None: (20, 0.9), "q25d75": (25, 0.75)}
+_refs = {}
+
+
+def kcountref(variant=None):
+    """The reference's own CPU kcount path, compiled unmodified against the one-rank stand-in headers
+    (oracle/Makefile `ref`, oracle/ref_driver.cpp), or None when oracle/_ref was not built."""
+    if variant in _refs:
+        return _refs[variant]
+    path = KCOUNTREF[variant]
+    if not path.exists():
+        return None
+    L = C.CDLL(str(path))
+    U64, VP, I = C.c_uint64, C.c_void_p, C.c_int
+    L.ref_last_error.restype = C.c_char_p
+    L.ref_build_params.argtypes = [VP, VP]
+    L.ref_build_params.restype = None
+    L.ref_kmer_from_string.argtypes = [C.c_char_p, I, I, VP]
+    L.ref_kmer_to_string.argtypes = [VP, I, I, C.c_char_p]
+    L.ref_get_kmers.argtypes = [C.c_char_p, C.c_int64, I, I, VP, C.c_int64]
+    L.ref_get_kmers.restype = C.c_int64
+    L.ref_kmer_revcomp.argtypes = [VP, I, I, VP]
+    L.ref_kmer_less.argtypes = [VP, VP, I, I]
+    L.ref_kmer_hash.argtypes = [VP, I, I, VP]
+    L.ref_get_minimizer_fast.argtypes = [VP, I, I, I, I, VP]
+    L.ref_minimizer_hash_fast.argtypes = [VP, I, I, I, VP]
+    L.ref_kmer_target_ranks.argtypes = [VP, U64, I, I, I, VP]
+    L.ref_analyze_kmers.argtypes = [I, I, I, I, I, VP, VP, U64, C.c_char_p, VP, VP, U64]
+    L.ref_analyze_kmers.restype = VP
+    L.ref_table_size.argtypes = [VP]
+    L.ref_table_size.restype = U64
+    L.ref_table_counters.argtypes = [VP, VP]
+    L.ref_table_counters.restype = None
+    L.ref_table_fetch.argtypes = [VP, VP, VP, VP, VP]
+    L.ref_table_fetch.restype = None
+    L.ref_table_free.argtypes = [VP]
+    L.ref_table_free.restype = None
+    qc, dyn = C.c_int(0), C.c_double(0)
+    L.ref_build_params(C.byref(qc), C.byref(dyn))
+    if (qc.value, dyn.value) != KCOUNTREF_PARAMS[variant]:
+        raise ImportError(f"{path} was built with KCOUNT_QUAL_CUTOFF={qc.value}, DYN_MIN_DEPTH={dyn.value}")
+    _refs[variant] = L
+    return L
+
+
+def _ref_check(L, rc, what):
+    if rc < 0:
+        raise ValueError(f"reference {what}: {L.ref_last_error().decode(errors='replace')}")
+    return rc
+
+
+class RefKmer:
+    """The reference's Kmer<MAX_K> layer (MAX_K = 32 * n_longs, n_longs = k // 32 + 1) at one k."""
+
+    def __init__(self, k: int, variant=None):
+        self.L, self.k, self.nl = kcountref(variant), k, k // 32 + 1
+
+    def _u64(self, fn, *args) -> int:
+        out = C.c_uint64(0)
+        _ref_check(self.L, fn(*args, C.byref(out)), fn.__name__)
+        return out.value
+
+    def from_string(self, s: str) -> np.ndarray:
+        assert len(s) == self.k
+        a = np.zeros(self.nl, dtype=np.uint64)
+        _ref_check(self.L, self.L.ref_kmer_from_string(s.encode(), self.k, self.nl, a.ctypes.data), "set_kmer")
+        return a
+
+    def to_string(self, longs) -> str:
+        a = np.ascontiguousarray(longs, dtype=np.uint64)
+        buf = C.create_string_buffer(self.k + 1)
+        _ref_check(self.L, self.L.ref_kmer_to_string(a.ctypes.data, self.k, self.nl, buf), "to_string")
+        return buf.value.decode()
+
+    def get_kmers(self, seq: str) -> np.ndarray:
+        cap = max(len(seq) - self.k + 1, 0) + 1
+        out = np.zeros((cap, self.nl), dtype=np.uint64)
+        n = _ref_check(self.L, self.L.ref_get_kmers(seq.encode(), len(seq), self.k, self.nl, out.ctypes.data, cap),
+                       "get_kmers")
+        return out[:n]
+
+    def revcomp(self, longs) -> np.ndarray:
+        a = np.ascontiguousarray(longs, dtype=np.uint64)
+        out = np.zeros_like(a)
+        _ref_check(self.L, self.L.ref_kmer_revcomp(a.ctypes.data, self.k, self.nl, out.ctypes.data), "revcomp")
+        return out
+
+    def less(self, a, b) -> bool:
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        return bool(_ref_check(self.L, self.L.ref_kmer_less(a.ctypes.data, b.ctypes.data, self.k, self.nl), "operator<"))
+
+    def hash(self, longs) -> int:
+        a = np.ascontiguousarray(longs, dtype=np.uint64)
+        return self._u64(self.L.ref_kmer_hash, a.ctypes.data, self.k, self.nl)
+
+    def minimizer_fast(self, longs, m: int, least_complement: bool = True) -> int:
+        a = np.ascontiguousarray(longs, dtype=np.uint64)
+        return self._u64(self.L.ref_get_minimizer_fast, a.ctypes.data, self.k, self.nl, m, int(least_complement))
+
+    def minimizer_hash_fast(self, longs, m: int) -> int:
+        a = np.ascontiguousarray(longs, dtype=np.uint64)
+        return self._u64(self.L.ref_minimizer_hash_fast, a.ctypes.data, self.k, self.nl, m)
+
+    def target_ranks(self, keys, world: int):
+        """(KmerDHT::get_kmer_target_rank of every row in a world of `world` ranks, the minimizer length the
+        KmerDHT constructor chose)."""
+        kk = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.nl)
+        out = np.zeros(kk.shape[0], dtype=np.int32)
+        m = _ref_check(self.L, self.L.ref_kmer_target_ranks(kk.ctypes.data, kk.shape[0], self.k, self.nl, world,
+                                                            out.ctypes.data), "get_kmer_target_rank")
+        return out, m
+
+
+class RefTable:
+    """The final table of the reference's analyze_kmers, with the run's warning and dropped-insert counts."""
+
+    def __init__(self, L, ptr, n_longs, k):
+        if not ptr:
+            raise ValueError(f"reference analyze_kmers: {L.ref_last_error().decode(errors='replace')}")
+        n = L.ref_table_size(ptr)
+        self.k, self.n_longs = k, n_longs
+        self.keys = np.empty((n, n_longs), dtype=np.uint64)
+        self.counts = np.empty(n, dtype=np.uint16)
+        self.left = np.empty(n, dtype=np.uint8)
+        self.right = np.empty(n, dtype=np.uint8)
+        L.ref_table_fetch(ptr, self.keys.ctypes.data, self.counts.ctypes.data, self.left.ctypes.data,
+                          self.right.ctypes.data)
+        c = np.zeros(2, dtype=np.int64)
+        L.ref_table_counters(ptr, c.ctypes.data)
+        self.warnings, self.dropped = int(c[0]), int(c[1])
+        L.ref_table_free(ptr)
+
+    def fetch(self):
+        return self.keys, self.counts, self.left, self.right
+
+
+def ref_analyze_kmers(packed_bytes, offsets, k, ctg_seqs=(), ctg_depths=(), dmin_thres=2, world=1, qual_offset=33,
+                      variant=None) -> RefTable:
+    """The reference's analyze_kmers (count_kmers, add_ctg_kmers when there are contigs, finish_updates) over
+    PackedRead bytes and contigs; qual_cutoff and dyn_min_depth are those of the build `variant`."""
+    L = kcountref(variant)
+    nl = k // 32 + 1
+    b = np.ascontiguousarray(packed_bytes, dtype=np.uint8)
+    o = np.ascontiguousarray(offsets, dtype=np.uint64)
+    blob = "".join(ctg_seqs).encode("ascii")
+    co = np.zeros(len(ctg_seqs) + 1, dtype=np.uint64)
+    np.cumsum([len(x) for x in ctg_seqs], out=co[1:])
+    d = np.ascontiguousarray(ctg_depths, dtype=np.uint16)
+    ptr = L.ref_analyze_kmers(k, nl, qual_offset, dmin_thres, world, b.ctypes.data, o.ctypes.data, o.size - 1, blob,
+                              co.ctypes.data, d.ctypes.data, len(ctg_seqs))
+    return RefTable(L, ptr, nl, k)
 
 
 class OracleTable:

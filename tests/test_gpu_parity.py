@@ -12,8 +12,8 @@ import pytest
 
 import mhm2_proxy_amd as m
 import oracle_lib as O
-from common import (GOLDEN, assert_tables_equal, ctg_set, edge_case_set, hot_set, oracle_ctg_table, oracle_table,
-                    read_reads_file, read_table_file, synth_set)
+from common import (GOLDEN, assert_tables_equal, ctg_set, edge_case_set, golden_input, hot_set, long_ragged_set,
+                    oracle_ctg_table, oracle_table, read_reads_file, read_table_file, ref_table, synth_set)
 
 pytestmark = pytest.mark.gpu
 
@@ -193,12 +193,24 @@ def test_empty_input():
         assert c.finish() == 0
 
 
-@pytest.mark.parametrize("name", sorted(p.name for p in GOLDEN.glob("table_*.tsv.gz")))
+@pytest.mark.parametrize("name", sorted(p.name for p in GOLDEN.glob("table_*.tsv.gz")
+                                         if not p.name.startswith("table_ctg_")))
 def test_golden_fixtures(name):
     _, setname, kk = name[:-len(".tsv.gz")].split("_")
     k = int(kk[1:])
     b, o = read_reads_file(GOLDEN / f"reads_{setname}.txt.gz")
     got, _ = hip_table(b, o, k)
+    assert_tables_equal(got, read_table_file(GOLDEN / name, k), name)
+
+
+@pytest.mark.parametrize("name", sorted(p.name for p in GOLDEN.glob("table_ctg_*.tsv.gz")))
+def test_golden_contig_fixtures(name):
+    """The golden set with contigs (reads_ctg, ctgs_ctg: 'seq depth' lines in the order they are applied) through
+    add_ctgs, against the table the reference's own analyze_kmers made of it (tests/golden/make_golden.py)."""
+    k = int(name[:-len(".tsv.gz")].split("_")[2][1:])
+    b, o, seqs, depths = golden_input("ctg")
+    got, st = ctg_table(b, o, seqs, depths, k)
+    assert st["ctg_kmers"] > 0
     assert_tables_equal(got, read_table_file(GOLDEN / name, k), name)
 
 
@@ -625,25 +637,6 @@ def test_c2_full_table_vs_cpu_restatement(k):
     assert_tables_equal(got, ref, f"C2 k={k}: GPU vs CPU restatement")
 
 
-def long_ragged_set(k: int, seed: int = 61):
-    """Reads of every awkward length for the valid-window list of the two-word extraction: empty, < k + 2,
-    k + 2 (one window), k + 3, 150, and reads far longer than a 2048-base tile (a read spanning several
-    tiles, starting before the tile it is counted in), concatenated in a random order."""
-    rng = np.random.default_rng(seed)
-    g = m.synth_genome(400_000, seed)
-    lens = [0, 1, k, k + 1, k + 2, k + 3, 150, 151, 2047, 2048, 2049, 4000, 9000]
-    reads = []
-    for i in range(600):
-        L = lens[i % len(lens)] if i % 3 else int(rng.integers(0, 300))
-        a = int(rng.integers(0, g.size - L - 1))
-        q = np.where(rng.random(L) < 0.03, 5, 31).astype(np.uint8)
-        reads.append((g[a:a + L] & 7) | (q << 3))
-    rng.shuffle(reads)
-    offs = np.zeros(len(reads) + 1, dtype=np.uint64)
-    np.cumsum([r.size for r in reads], out=offs[1:])
-    return np.concatenate(reads).astype(np.uint8), offs
-
-
 @pytest.mark.parametrize("k", [33, 47, 63, 77, 99, 21])
 def test_valid_window_walk_long_and_ragged_reads(k, knob):
     """Two-word extraction over the listed valid windows == the oracle, for reads of length 0 .. 9000 (reads
@@ -755,3 +748,54 @@ def test_fetch_staged_chunk_tails(chunk, knob):
         assert np.array_equal(a.keys, e.keys) and np.array_equal(a.counts, e.counts)
         assert np.array_equal(a.left, e.left) and np.array_equal(a.right, e.right)
     assert np.isin(got.left.view(np.uint8), np.frombuffer(b"ACGTXF", np.uint8)).all()
+
+
+# ---- the reference's own CPU code, built single-rank (oracle/_ref/libkcountref.so) ----------------------------------
+
+def _ref_input(kind, k, dmin):
+    if kind == "synth":
+        return synth_set(2000, 10000, 100 + k) + ((), ())
+    if kind == "edge":
+        return edge_case_set() + ((), ())
+    if kind == "hot":
+        return hot_set() + ((), ())
+    if kind == "sweeps":  # test_forced_overflow_sweeps' input
+        return synth_set(3000, 50000, 13) + ((), ())
+    if kind == "passes":  # test_finish_passes_vs_oracle's input
+        return synth_set(2500, 12000, 600 + k) + ((), ())
+    return ctg_set(seed=40 + k + dmin)
+
+
+@pytest.mark.parametrize("kind,k,dmin", [
+    ("synth", 21, 2), ("synth", 33, 2), ("synth", 63, 2), ("synth", 77, 2), ("synth", 99, 2), ("synth", 127, 2),
+    ("edge", 21, 2), ("edge", 63, 2), ("hot", 21, 2),
+    ("ctg", 21, 2), ("ctg", 63, 2), ("ctg", 99, 2), ("ctg", 21, 1), ("ctg", 21, 3),
+    ("sweeps", 63, 2), ("passes", 21, 2)])
+def test_hip_vs_reference_build(kind, k, dmin, knob, monkeypatch):
+    """The HIP table, row for row, against the table the reference's own analyze_kmers makes of the same input: its
+    unmodified kmer.cpp, kcount.cpp, kcount_cpu.cpp and kmer_dht.cpp compiled against one-rank stand-in headers
+    (oracle/Makefile `ref`), so no restatement by this project stands between the kernels and MetaHipMer2's code.
+    Reads only, then reads and contigs through add_ctgs; one case over forced overflow sweeps (64-slot tables, one
+    fine bucket) and one over three finish passes."""
+    if O.kcountref() is None:
+        pytest.skip("oracle/_ref/libkcountref.so not built (reference tree absent)")
+    b, o, seqs, depths = _ref_input(kind, k, dmin)
+    exp = ref_table(b, o, k, seqs, depths, dmin_thres=dmin)
+    assert len(exp) > 1000
+    if kind == "hot":
+        assert (exp.counts == 65535).any(), "fixture must saturate a count"
+    if kind == "sweeps":
+        knob("cap", 64)
+        knob("fine_bits", 0)
+    elif kind == "passes":
+        monkeypatch.setenv("MHMKC_PASSES", "3")
+    if len(seqs):
+        got, st = ctg_table(b, o, seqs, depths, k, dmin_thres=dmin)
+        assert st["ctg_kmers"] > 0
+    else:
+        got, st = hip_table(b, o, k, batches=2 if kind == "passes" else 1, dmin_thres=dmin)
+    if kind == "sweeps":
+        assert st["overflow_sweeps"] > 0
+    elif kind == "passes":
+        assert st["finish_passes"] == 3
+    assert_tables_equal(got, exp, f"HIP vs reference build: {kind} k={k} dmin={dmin}")

@@ -55,6 +55,22 @@ def test_minimizer_hash_random_keys_full_width(k):
     assert bad.size == 0, f"k={k}: {bad.size} of {n} differ, first row {bad[:1]}"
 
 
+@pytest.mark.parametrize("k", [21, 63, 77])
+def test_target_ranks_vs_reference_build(k):
+    """The device's owner ranks against the reference's own KmerDHT::get_kmer_target_rank (oracle/_ref/
+    libkcountref.so: its kmer.cpp, kmer_dht.cpp and hash_funcs.c compiled unmodified, one rank pretending a world of
+    8), not the oracle's restatement of it."""
+    if O.kcountref() is None:
+        pytest.skip("oracle/_ref/libkcountref.so not built (reference tree absent)")
+    keys = random_canonical_keys(300, k, k // 32 + 1, seed=1000 + k)
+    exp, mlen = O.RefKmer(k).target_ranks(keys, 8)
+    assert mlen == m.kcount.minimizer_len(k)
+    assert len(set(exp.tolist())) == 8, "300 keys must reach every rank"
+    with m.KmerCounter(k, device=0) as c:
+        got = c.target_ranks(keys, 8)
+    assert (np.asarray(got).astype(np.int64) == exp).all(), f"k={k}"
+
+
 def test_minimizer_hash_explicit_m_and_wide_longs():
     """An explicit m (1..min(k, 28)) and keys given with more longs than k needs (a larger MAX_K)."""
     k = 45

@@ -1,5 +1,11 @@
 """Pinning the CPU oracle (runs without a GPU).
 
+The checking chain is: reference build -> oracle and literal restatement -> golden fixtures -> GPU. Its top, the
+reference's own kcount sources compiled single-rank (oracle/_ref/libkcountref.so), is compared with the oracle in
+tests/test_reference_build.py; the golden tables are that build's output (tests/golden/make_golden.py). Still
+unpinned by reference code: the multi-rank exchange over real UPC++, FASTQ ingest, merge_reads, and k < 15 or
+k % 32 == 0, where the reference is undefined or wrong. This file holds the links below the top:
+
   1. MurmurHash3 / quick_hash == the reference's own src/hash_funcs.c compiled unmodified (oracle/_ref);
   2. SURVEY.md Appendix A known answers (Kmer layout, hash, minimizer, minimizer hash);
   3. the invariants of the reference's test/kmer-test.cpp (round trip, revcomp, hash, minimizers);
@@ -15,8 +21,8 @@ import pytest
 import mhm2_proxy_amd as m
 import oracle_lib as O
 import ref_literal as R
-from common import (GOLDEN, assert_tables_equal, ctg_set, edge_case_set, oracle_ctg_table, oracle_table, read_reads_file,
-                    read_table_file, synth_set)
+from common import (GOLDEN, assert_tables_equal, ctg_set, edge_case_set, golden_input, oracle_ctg_table, oracle_table,
+                    read_reads_file, read_table_file, synth_set)
 
 # test/kmer-test.cpp:11-33 (data vectors of the reference's own unit test)
 RANDOM_READ = ("CGCTGTTCCAGATGACGAACCAGGAATTCCGCCAGGTATTCGACTTTATTCGCGAAGTCAAGAAGTTGAACGTCATCAGTGTGAACTACGGTTGCGAAGG"
@@ -170,8 +176,9 @@ def test_dynamic_threshold_quirk():
 def test_oracle_reproduces_golden(name):
     _, setname, kk = name[:-len(".tsv.gz")].split("_")
     k = int(kk[1:])
-    b, o = read_reads_file(GOLDEN / f"reads_{setname}.txt.gz")
-    assert_tables_equal(oracle_table(b, o, k), read_table_file(GOLDEN / name, k), name)
+    b, o, seqs, depths = golden_input(setname)
+    got = oracle_ctg_table(b, o, seqs, depths, k) if seqs else oracle_table(b, o, k)
+    assert_tables_equal(got, read_table_file(GOLDEN / name, k), name)
 
 
 def test_golden_s100_literal_k21():
@@ -232,12 +239,17 @@ def test_mt_restatement_parameters(cutoff, dmin, dyn):
 
 @pytest.mark.parametrize("name", sorted(p.name for p in GOLDEN.glob("table_*.tsv.gz")))
 def test_mt_restatement_reproduces_golden(name):
-    from common import GOLDEN, assert_tables_equal, read_reads_file, read_table_file
+    from common import GOLDEN, assert_tables_equal, golden_input, read_table_file
 
     _, setname, kk = name[:-len(".tsv.gz")].split("_")
     k = int(kk[1:])
-    b, o = read_reads_file(GOLDEN / f"reads_{setname}.txt.gz")
-    t = O.kcount_mt(b, o, k, threads=4)
+    b, o, seqs, depths = golden_input(setname)
+    if seqs:
+        offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        np.cumsum([len(x) for x in seqs], out=offs[1:])
+        t = O.kcount_mt_ctgs(b, o, "".join(seqs).encode(), offs, depths, k, threads=4)
+    else:
+        t = O.kcount_mt(b, o, k, threads=4)
     keys, c, l, r = t.fetch()
     assert_tables_equal(m.KmerTable(k, keys, c, l, r), read_table_file(GOLDEN / name, k), name)
 
