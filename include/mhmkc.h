@@ -314,6 +314,47 @@ void mhmkc_host_free(void *p);
 int mhmkc_device_output(mhmkc_t h, const uint64_t **d_keys, const uint16_t **d_counts, const char **d_left,
                         const char **d_right, uint64_t *n_out);
 
+/* Point queries on the finished table, answered on the GPU. "Row i" is row i of mhmkc_fetch / mhmkc_device_output.
+ * The first query after a finish builds a device index over the rows (8 bytes per slot, a power of two >= 2 n_out
+ * slots, counted in mhmkc_stats.device_bytes[_peak]); it is dropped at the next reset, finish or destroy. At most
+ * 2^32-2 rows (MHMKC_EUNSUPPORTED beyond). Before finish: MHMKC_ESTATE. */
+#define MHMKC_NO_ROW 0xFFFFFFFFu
+
+/* KmerDHT::get_local_kmer_counts / kmer_exists (src/kcount/kmer_dht.cpp:198-219) for n k-mers at once. keys:
+ * n * n_longs words in Kmer::longs layout (the handle's n_longs; the unused low bits of the last key word are ignored).
+ * canonicalize = 0 looks the key up as given (get_local_kmer_counts), 1 looks up min(key, revcomp(key)) (kmer_exists);
+ * left / right are the stored (canonical-frame) extensions in both cases. Output i belongs to query i; a miss gives
+ * rows[i] = MHMKC_NO_ROW, counts[i] = 0, left[i] = right[i] = 0. Any output pointer may be NULL. With n_ranks > 1 the
+ * call answers for this rank's rows only (get_local_kmer_counts). Host arrays: staged through the device in chunks. */
+int mhmkc_lookup(mhmkc_t h, const uint64_t *keys, uint64_t n, int canonicalize, uint32_t *rows, uint16_t *counts,
+                 char *left, char *right);
+/* Same with device arrays, asynchronous on the handle's stream (inputs written on another stream: mhmkc_wait_stream
+ * first; the outputs are complete once the handle's stream has reached this point). */
+int mhmkc_lookup_device(mhmkc_t h, const uint64_t *d_keys, uint64_t n, int canonicalize, uint32_t *d_rows,
+                        uint16_t *d_counts, char *d_left, char *d_right);
+
+enum {
+  MHMKC_LINK_OK = 0,       /* next is the neighbour's row and its extension leads back */
+  MHMKC_LINK_DEADEND = 1,  /* an 'X' on the row or the neighbour, or the neighbour is not in the table */
+  MHMKC_LINK_FORK = 2,     /* an 'F' on the row or the neighbour */
+  MHMKC_LINK_CONFLICT = 3, /* the neighbour's extension does not lead back */
+  MHMKC_LINK_RC = 0x80     /* or-ed into OK: the neighbour is entered reverse-complemented */
+};
+/* get_next_step (src/dbjg_traversal.cpp:165-239) for every row and both directions, without the visited state: entry
+ * d * n_out + i describes row i in direction d (0 LEFT, 1 RIGHT), in row i's stored (canonical) orientation.
+ *   1. row i's own left or right is 'X': DEADEND; else either is 'F': FORK; next = MHMKC_NO_ROW, nothing looked up;
+ *   2. the neighbour is kmer.forward_base(right) (RIGHT) / kmer.backward_base(left) (LEFT); is_rc = revcomp(neighbour)
+ *      < neighbour; the smaller of the two is looked up; not in the table: DEADEND, next = MHMKC_NO_ROW;
+ *   3. otherwise next = the neighbour's row j; DEADEND if row j has an 'X', else FORK if it has an 'F', else with j's
+ *      extensions oriented (complemented and swapped when is_rc): RIGHT needs j's left == kmer.front(), LEFT j's right
+ *      == kmer.back(); no: CONFLICT, yes: OK (| MHMKC_LINK_RC when is_rc).
+ * A walker over next / status needs no hashing and no k-mer arithmetic; the visited marks (REPEAT / VISITED) stay
+ * with it. Single-rank handles only (MHMKC_EUNSUPPORTED with n_ranks > 1, checked before the state). Host arrays of
+ * 2 * n_out entries (either may be NULL). */
+int mhmkc_dbjg_links(mhmkc_t h, uint32_t *next, uint8_t *status);
+/* The same arrays on the device, computed once per finish and kept until the next reset / finish / destroy. */
+int mhmkc_dbjg_links_device(mhmkc_t h, const uint32_t **d_next, const uint8_t **d_status);
+
 /* Host-staged exchange between ranks (instead of RCCL): for n_ranks > 1 with comm_id == NULL, set before
  * the first mhmkc_finish. Every rank's callbacks are called collectively, in the same order on all ranks, with
  * host buffers; a callback returns 0 on success.

@@ -34,7 +34,10 @@ extern "C" {
  *                 much slower than the wire runs, 0 never, 2 every other chunk
  *   local_rounds  0: one rank's host batches are fine-partitioned at finish, not chunk by chunk as they land (created
  *                 handles)
- *   cb0, cb0_2, cb0_3  coarse bits for one-, two-, three/four-word keys (0: 8, 8, 7) */
+ *   cb0, cb0_2, cb0_3  coarse bits for one-, two-, three/four-word keys (0: 8, 8, 7)
+ *   query_slots_log2   the query index (mhmkc_lookup, mhmkc_dbjg_links) gets exactly 2^v slots (0: the smallest power
+ *                 of two >= 2 n_out); the query fails with MHMKC_EINVAL if 2^v <= n_out. A load near 1 exercises long
+ *                 probe chains and the wrap past the last slot */
 int mhmkc_debug_set(const char *knob, int64_t value);
 /* Every knob back to its default. */
 void mhmkc_debug_reset(void);

@@ -984,6 +984,41 @@ class HashTableInserter {
     check(mhmkc_get_stats(h_, &s), h_, "mhmkc_get_stats");
     return s;
   }
+  mhmkc_t handle() const { return h_; }  // for the C ABI calls this class does not wrap (mhmkc_fetch, ...)
+  // get_local_kmer_counts (canonicalize = false) / kmer_exists (true) for a batch of k-mers, answered on the GPU from
+  // the finished table (mhmkc_lookup), without the KmerMap: out[i] / found[i] belong to kmers[i] (a miss: found 0 and
+  // an empty KmerCounts)
+  void lookup(const std::vector<Kmer<MAX_K>> &kmers, bool canonicalize, std::vector<KmerCounts> &out,
+              std::vector<uint8_t> &found) {
+    const size_t n = kmers.size();
+    constexpr int NLG = Kmer<MAX_K>::N_LONGS;
+    std::vector<uint64_t> keys(n * NLG);
+    for (size_t i = 0; i < n; i++) std::memcpy(&keys[i * NLG], kmers[i].get_longs(), 8 * NLG);
+    std::vector<uint32_t> rows(n);
+    std::vector<uint16_t> counts(n);
+    std::vector<char> left(n), right(n);
+    check(mhmkc_lookup(h_, keys.data(), n, canonicalize ? 1 : 0, rows.data(), counts.data(), left.data(), right.data()),
+          h_, "mhmkc_lookup");
+    out.assign(n, KmerCounts());
+    found.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+      if (rows[i] == MHMKC_NO_ROW) continue;
+      found[i] = 1;
+      out[i].count = counts[i];
+      out[i].left = left[i];
+      out[i].right = right[i];
+    }
+  }
+  // the de Bruijn links of every row of the finished table (mhmkc_dbjg_links: the lookup of get_next_step,
+  // src/dbjg_traversal.cpp:165-239, for all rows at once): next / status get 2 * n_out entries, entry d * n_out + i =
+  // row i (of mhmkc_fetch) in direction d (0 LEFT, 1 RIGHT)
+  void dbjg_links(std::vector<uint32_t> &next, std::vector<uint8_t> &status) {
+    uint64_t n = 0;
+    check(mhmkc_device_output(h_, nullptr, nullptr, nullptr, nullptr, &n), h_, "mhmkc_device_output");
+    next.assign(2 * n, MHMKC_NO_ROW);
+    status.assign(2 * n, 0);
+    check(mhmkc_dbjg_links(h_, next.data(), status.data()), h_, "mhmkc_dbjg_links");
+  }
 };
 
 template <int MAX_K>
@@ -1018,6 +1053,17 @@ class KmerDHT {
   KmerCounts *get_local_kmer_counts(const Kmer<MAX_K> &kmer) {
     auto it = local_kmers.find(kmer);
     return it == local_kmers.end() ? nullptr : &it->second;
+  }
+  // src/kcount/kmer_dht.cpp:206-219 for this rank's k-mers (the reference's RPC to the owner rank is the caller's)
+  bool kmer_exists(Kmer<MAX_K> kmer_fw) {
+    const Kmer<MAX_K> kmer_rc = kmer_fw.revcomp();
+    const Kmer<MAX_K> *kmer = (kmer_rc < kmer_fw) ? &kmer_rc : &kmer_fw;
+    return local_kmers.find(*kmer) != local_kmers.end();
+  }
+  // the batch form on the GPU, from the finished table itself (HashTableInserter::lookup, mhmkc_lookup)
+  void lookup(const std::vector<Kmer<MAX_K>> &kmers, bool canonicalize, std::vector<KmerCounts> &out,
+              std::vector<uint8_t> &found) {
+    ht_inserter.lookup(kmers, canonicalize, out, found);
   }
   // src/kcount/kmer_dht.cpp:193-196: minimizer_hash_fast(minimizer_len) % rank_n (the same for a k-mer and its
   // reverse complement); after finish every local k-mer satisfies it (MHMKC_OWNER_MINIMIZER)

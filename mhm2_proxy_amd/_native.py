@@ -32,6 +32,9 @@ ERRORS = {
 MHMKC_OWNER_HASH = 0
 MHMKC_OWNER_MINIMIZER = 1
 
+MHMKC_NO_ROW = 0xFFFFFFFF
+MHMKC_LINK_OK, MHMKC_LINK_DEADEND, MHMKC_LINK_FORK, MHMKC_LINK_CONFLICT, MHMKC_LINK_RC = 0, 1, 2, 3, 0x80
+
 STAGES = ["tileidx", "extract_hist", "extract_scatter", "exchange", "part_hist", "part_scatter", "count", "other"]
 
 # every symbol include/mhmkc.h declares (checked by tests/test_abi.py)
@@ -46,6 +49,7 @@ ABI_SYMBOLS = [
     "mhmkc_add_fastq_file", "mhmkc_add_fastq_pairs_file",
     "mhmkc_fastq_packed", "mhmkc_fastq_fetch",
     "mhmkc_wait_stream", "mhmkc_set_dmin_thres", "mhmkc_set_transport", "mhmkc_minimizer_hashes",
+    "mhmkc_lookup", "mhmkc_lookup_device", "mhmkc_dbjg_links", "mhmkc_dbjg_links_device",
 ]
 SYNTH_SYMBOLS = ["mhmkc_synth_config_init", "mhmkc_synth_genome", "mhmkc_synth_reads"]
 # the test-only entry point (include/mhmkc_debug.h)
@@ -243,6 +247,10 @@ def lib() -> C.CDLL:
     L.mhmkc_set_dmin_thres.argtypes = [VP, C.c_int32]
     L.mhmkc_set_transport.argtypes = [VP, P(MhmkcTransport)]
     L.mhmkc_minimizer_hashes.argtypes = [VP, VP, U64, C.c_int32, C.c_int32, VP]
+    L.mhmkc_lookup.argtypes = [VP, VP, U64, I32, VP, VP, VP, VP]
+    L.mhmkc_lookup_device.argtypes = [VP, VP, U64, I32, VP, VP, VP, VP]
+    L.mhmkc_dbjg_links.argtypes = [VP, VP, VP]
+    L.mhmkc_dbjg_links_device.argtypes = [VP, P(VP), P(VP)]
     _lib = L
     return L
 

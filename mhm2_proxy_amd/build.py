@@ -5,6 +5,7 @@
   oracle/liboracle.so (+ _ref/)     make -C oracle: the CPU checker (test infrastructure only)
   tools/bin/kmermap_fill            g++: KmerMap fill timing of the C++ adapter from table files (tests, bench.py)
   tools/bin/libmhmkc_handoff.so     g++: the adapter's streamed hand-off (load_ordered) timed in bench.py's process
+  tools/bin/libmhmkc_qfind.so       g++: hand-off + KmerMap::find on query keys, timed in tools/query_bench.py's process
 
 Incremental: a target is rebuilt only when one of its sources is newer; libmhmkc.so also when the build id it
 carries (the SHA-256 of its sources, mhmkc_build_id) is not the tree's, whatever the file times say.
@@ -27,7 +28,8 @@ LIB = PKG / "libmhmkc.so"
 SYNTH = PKG / "libmhmkc_synth.so"
 ORACLE = ROOT / "oracle" / "liboracle.so"
 
-LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kcount_owner.hip", CSRC / "fastq.hip",
+LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kcount_owner.hip", CSRC / "kcount_query.hip",
+               CSRC / "fastq.hip",
                CSRC / "mhmkc_host.cpp"]
 LIB_DEPS = LIB_SOURCES + [CSRC / "kcount_launch.hpp", CSRC / "kmer_ops.hpp", ROOT / "include" / "mhmkc.h"]
 SYNTH_DEPS = [CSRC / "synth.c", ROOT / "include" / "mhmkc_synth.h"]
@@ -35,6 +37,9 @@ FILL = ROOT / "tools" / "bin" / "kmermap_fill"
 FILL_DEPS = [ROOT / "tools" / "cpp" / "kmermap_fill.cpp", ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]
 HANDOFF = ROOT / "tools" / "bin" / "libmhmkc_handoff.so"
 HANDOFF_DEPS = [ROOT / "tools" / "cpp" / "handoff.cpp", ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]
+# tools/query_bench.py's comparison route: the hand-off into a KmerMap, then KmerMap::find on the query keys
+QFIND = ROOT / "tools" / "bin" / "libmhmkc_qfind.so"
+QFIND_DEPS = [ROOT / "tools" / "cpp" / "query_find.cpp", ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]
 # test infrastructure: the restated traversal over a given table (the multi-rank multi-k chain, tests/test_c5_scale.py)
 DBJG = ROOT / "tools" / "bin" / "libmhmkc_dbjg.so"
 DBJG_DEPS = [ROOT / "tools" / "cpp" / "dbjg_lib.cpp", ROOT / "include" / "mhmkc_dbjg.hpp",
@@ -164,6 +169,16 @@ def build_dbjg(force: bool = False) -> Path:
     return DBJG
 
 
+def build_qfind(force: bool = False) -> Path:
+    if force or _stale(QFIND, QFIND_DEPS + [LIB]):
+        QFIND.parent.mkdir(parents=True, exist_ok=True)
+        tmp = QFIND.with_suffix(".tmp")
+        _run(["g++", "-O2", "-std=c++17", "-pthread", "-fPIC", "-shared", "-I", ROOT / "include", QFIND_DEPS[0], "-L",
+              PKG, "-lmhmkc", "-lz", "-Wl,-rpath,$ORIGIN/../../mhm2_proxy_amd", "-o", tmp])
+        tmp.replace(QFIND)
+    return QFIND
+
+
 def build_all(force: bool = False) -> None:
     build_lib(force)
     build_synth(force)
@@ -171,6 +186,7 @@ def build_all(force: bool = False) -> None:
     build_fill(force)
     build_handoff(force)
     build_dbjg(force)
+    build_qfind(force)
 
 
 if __name__ == "__main__":

@@ -409,4 +409,26 @@ hipError_t launch_owner_hist(const uint64_t *keys, uint64_t n, int nlo, int k, i
 hipError_t launch_owner_scatter(const OutRows &in, uint64_t n, int nlo, const uint8_t *dest, int n_ranks,
                                 unsigned long long *cursor, const OutRows &out, hipStream_t s);
 
+// Queries on the finished table (kcount_query.hip): an open-addressing index over the output rows, 8-byte slots
+// row | tag << 32 (tag = the low 32 bits of mhmkc_map_hash, home slot = hash >> shift, linear probing, an empty slot
+// all ones). slots holds mask + 1 entries (a power of two > n_rows), set to 0xFF bytes before launch_query_build.
+struct QueryIndex {
+  unsigned long long *slots;
+  uint64_t mask;    // capacity - 1
+  uint64_t n_rows;  // rows of the table it indexes (< 2^32 - 1)
+  int shift;        // 64 - log2(capacity)
+};
+hipError_t preload_query_kernels();
+// nl = k/32 + 1 key words (1..4) of the nlo words per row / query
+hipError_t launch_query_build(const uint64_t *keys, uint64_t n, int nl, int nlo, const QueryIndex &ix, hipStream_t s);
+// rows[i] = the row of query i (0xFFFFFFFF: not in the table), counts / left / right its fields (0 on a miss); any
+// output may be null. canonicalize: min(key, revcomp(key)) is looked up. The unused low bits of a query's last word
+// are ignored.
+hipError_t launch_query_lookup(const uint64_t *q, uint64_t n, bool canonicalize, int k, int nl, int nlo,
+                               const QueryIndex &ix, const OutRows &t, uint32_t *rows, uint16_t *counts, char *left,
+                               char *right, hipStream_t s);
+// next / status [2 * n]: entry d * n + i = row i's de Bruijn neighbour in direction d (mhmkc_dbjg_links)
+hipError_t launch_dbjg_links(const OutRows &t, uint64_t n, int k, int nl, int nlo, const QueryIndex &ix, uint32_t *next,
+                             uint8_t *status, hipStream_t s);
+
 }  // namespace mhm

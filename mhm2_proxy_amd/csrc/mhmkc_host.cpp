@@ -66,6 +66,7 @@ struct DebugKnobs {
   int64_t h2d_nib = -1;       // H2D of a host batch: 1 nibbles + u32 offsets, 2 nibbles + u64 offsets, 0 the PackedRead
                               // bytes, -1 1 with >= 4 host threads, else 0
   int64_t cb0[4] = {0, 0, 0, 0};  // coarse bits by key words (0: the default)
+  int64_t query_slots_log2 = 0;   // slots of the query index, as a power of two (0: the smallest one >= 2 n_out)
 };
 DebugKnobs g_dbg;
 
@@ -466,6 +467,27 @@ struct mhmkc {
   DevBuf d_mslot;
   uint64_t map_cap = 0;  // the capacity d_mslot holds the slots of (0: none; cleared with ord_ready)
   int map_slots(uint64_t cap);
+  // queries on the finished table (kcount_query.hip): the index over the output rows, built by the
+  // first query after a finish; the de Bruijn links of every row (next u32 [2 n_out], then status u8 [2 n_out]); the
+  // device staging of one chunk of a host lookup. All dropped by drop_query (reset, the next finish, destroy).
+  DevBuf d_qidx, d_links, d_qstage;
+  mhm::QueryIndex qidx{};
+  bool qidx_ready = false, links_ready = false;
+  mhm::OutRows out_rows() const {
+    return mhm::OutRows{d_out_keys.as<uint64_t>(), d_out_counts.as<uint16_t>(), d_out_left.as<char>(),
+                        d_out_right.as<char>()};
+  }
+  int query_index();
+  int lookup_device(const uint64_t *d_keys, uint64_t n, int canonicalize, uint32_t *d_rows, uint16_t *d_counts,
+                    char *d_left, char *d_right);
+  int dbjg_links();
+  void drop_query() {
+    d_qidx.release();
+    d_links.release();
+    d_qstage.release();
+    qidx = mhm::QueryIndex{};
+    qidx_ready = links_ready = false;
+  }
   DevBuf d_spill;  // k_count: the deferred records of cold sweeps, mhm::SPILL_RECORDS per persistent workgroup
   DevBuf d_cfit;   // capped fine layout: per coarse bucket of the pass its first record and fine-bucket capacity
   DevBuf d_inc_skip;  // incremental count: per owned coarse bucket, 1 = overflowed its capped layout (k_inc_fixup)
@@ -2299,6 +2321,7 @@ int mhmkc::finish(uint64_t *n_out_ret) {
   int rc = begin_round();
   if (rc) return rc;
   ord_ready = false;
+  drop_query();
   ctg_gathered = false;
   if ((rc = resolve_slabs())) return rc;
   hipError_t e;
@@ -3060,6 +3083,7 @@ int mhmkc_create(mhmkc_t *out, const mhmkc_config *cfg) {
     return MHMKC_EHIP;
   }
   (void)mhm::preload_owner_kernels();  // (the hand-off's code object: loaded here, not in the first fetch)
+  (void)mhm::preload_query_kernels();  // (and the query kernels': not in the first lookup)
   if (cfg->n_ranks > 1 && cfg->comm_id) {
     ncclUniqueId id;
     memcpy(&id, cfg->comm_id, sizeof id);
@@ -3124,6 +3148,7 @@ void mhmkc_destroy(mhmkc_t h) {
                     &h->d_fq_text,  &h->d_fq_chunk,   &h->d_fq_lines,   &h->d_fq_len,     &h->d_fq_tmp,
                     &h->d_fq_bytes, &h->d_fq_offs,    &h->d_fq_err};
   for (DevBuf *b : bufs) b->release();
+  h->drop_query();
   DevBuf *cbufs[] = {&h->d_ctg_bytes, &h->d_ctg_offs, &h->d_ctg_win,   &h->d_ctg_depth, &h->d_ctg_scratch,
                      &h->d_ctg_state, &h->d_ctg_bucket, &h->d_ctg_done, &h->d_ctg_keys[0], &h->d_ctg_keys[1],
                      &h->d_ctg_keys[2], &h->d_ctg_keys[3]};
@@ -3877,6 +3902,142 @@ int mhmkc_device_output(mhmkc_t h, const uint64_t **d_keys, const uint16_t **d_c
   return MHMKC_OK;
 }
 
+// The index of the query kernels over the output rows (built once per finish, on the handle's stream).
+int mhmkc::query_index() {
+  if (qidx_ready) return MHMKC_OK;
+  const uint64_t n = n_out;
+  if (n >= 0xffffffffull) return fail(MHMKC_EUNSUPPORTED, "table queries: at most 2^32-2 rows");
+  const int64_t v = g_dbg.query_slots_log2;
+  int log2cap = 1;
+  if (v != 0) {
+    if (v < 1 || v > 40 || (1ull << v) <= n)
+      return fail(MHMKC_EINVAL, "query_slots_log2 = %lld: the index needs more than n_out = %llu slots", (long long)v,
+                  (unsigned long long)n);
+    log2cap = (int)v;
+  } else {
+    while ((1ull << log2cap) < 2 * n) log2cap++;
+  }
+  const uint64_t cap = 1ull << log2cap;
+  hipError_t e;
+  if ((e = grow(d_qidx, cap * 8)) != hipSuccess)
+    return e == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "query index: %llu bytes", (unsigned long long)(cap * 8))
+                                    : hip_fail(e, "query index");
+  qidx = mhm::QueryIndex{d_qidx.as<unsigned long long>(), cap - 1, n, 64 - log2cap};
+  if ((e = hipMemsetAsync(d_qidx.p, 0xFF, cap * 8, stream)) != hipSuccess ||
+      (e = mhm::launch_query_build(d_out_keys.as<uint64_t>(), n, nl, nlo, qidx, stream)) != hipSuccess)
+    return hip_fail(e, "query index build");
+  qidx_ready = true;
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return MHMKC_OK;
+}
+
+int mhmkc::lookup_device(const uint64_t *d_keys, uint64_t n, int canonicalize, uint32_t *d_rows, uint16_t *d_counts,
+                         char *d_left, char *d_right) {
+  if (!n) return MHMKC_OK;
+  hipError_t e = hipSuccess;
+  if (!n_out) {  // an empty table: every query misses, no kernel runs
+    if (d_rows) e = hipMemsetAsync(d_rows, 0xFF, n * 4, stream);
+    if (e == hipSuccess && d_counts) e = hipMemsetAsync(d_counts, 0, n * 2, stream);
+    if (e == hipSuccess && d_left) e = hipMemsetAsync(d_left, 0, n, stream);
+    if (e == hipSuccess && d_right) e = hipMemsetAsync(d_right, 0, n, stream);
+    return e == hipSuccess ? MHMKC_OK : hip_fail(e, "lookup");
+  }
+  int rc = query_index();
+  if (rc) return rc;
+  if ((e = mhm::launch_query_lookup(d_keys, n, canonicalize != 0, k, nl, nlo, qidx, out_rows(), d_rows, d_counts, d_left,
+                                    d_right, stream)) != hipSuccess)
+    return hip_fail(e, "lookup");
+  return MHMKC_OK;
+}
+
+int mhmkc::dbjg_links() {
+  if (links_ready) return MHMKC_OK;
+  const uint64_t n = n_out;
+  if (n) {
+    int rc = query_index();
+    if (rc) return rc;
+    hipError_t e;
+    if ((e = grow(d_links, 2 * n * 5 + 64)) != hipSuccess) return hip_fail(e, "dbjg links");
+    uint32_t *next = d_links.as<uint32_t>();
+    if ((e = mhm::launch_dbjg_links(out_rows(), n, k, nl, nlo, qidx, next, (uint8_t *)(next + 2 * n), stream)) !=
+        hipSuccess)
+      return hip_fail(e, "dbjg links");
+    st.device_bytes = g_dev_live.load();
+    st.device_bytes_peak = g_dev_peak.load();
+  }
+  links_ready = true;
+  return MHMKC_OK;
+}
+
+int mhmkc_lookup_device(mhmkc_t h, const uint64_t *d_keys, uint64_t n, int canonicalize, uint32_t *d_rows,
+                        uint16_t *d_counts, char *d_left, char *d_right) {
+  if (!h) return MHMKC_EINVAL;
+  if (!h->finished) return h->fail(MHMKC_ESTATE, "lookup before finish");
+  if (n && !d_keys) return h->fail(MHMKC_EINVAL, "null key buffer");
+  return h->lookup_device(d_keys, n, canonicalize, d_rows, d_counts, d_left, d_right);
+}
+
+int mhmkc_lookup(mhmkc_t h, const uint64_t *keys, uint64_t n, int canonicalize, uint32_t *rows, uint16_t *counts,
+                 char *left, char *right) {
+  if (!h) return MHMKC_EINVAL;
+  if (!h->finished) return h->fail(MHMKC_ESTATE, "lookup before finish");
+  if (n && !keys) return h->fail(MHMKC_EINVAL, "null key buffer");
+  if (!n) return MHMKC_OK;
+  // chunks of the batch through one device staging buffer: keys in, the four outputs back
+  const uint64_t CH = std::min<uint64_t>(n, 1ull << 20);
+  const size_t kb = align_up(CH * 8 * h->nlo, 256), rb = align_up(CH * 4, 256), cb = align_up(CH * 2, 256),
+               lb = align_up(CH, 256);
+  hipError_t e;
+  if ((e = h->grow(h->d_qstage, kb + rb + cb + 2 * lb)) != hipSuccess) return h->hip_fail(e, "lookup staging");
+  char *base = h->d_qstage.as<char>();
+  uint64_t *dk = (uint64_t *)base;
+  uint32_t *dr = (uint32_t *)(base + kb);
+  uint16_t *dc = (uint16_t *)(base + kb + rb);
+  char *dl = base + kb + rb + cb, *drt = dl + lb;
+  for (uint64_t i0 = 0; i0 < n; i0 += CH) {
+    const uint64_t m = std::min(CH, n - i0);
+    if ((e = hipMemcpyAsync(dk, keys + i0 * h->nlo, m * 8 * h->nlo, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+      return h->hip_fail(e, "lookup H2D");
+    int rc = h->lookup_device(dk, m, canonicalize, rows ? dr : nullptr, counts ? dc : nullptr, left ? dl : nullptr,
+                              right ? drt : nullptr);
+    if (rc) return rc;
+    if (rows) e = h->d2h(rows + i0, dr, m * 4);
+    if (e == hipSuccess && counts) e = h->d2h(counts + i0, dc, m * 2);
+    if (e == hipSuccess && left) e = h->d2h(left + i0, dl, m);
+    if (e == hipSuccess && right) e = h->d2h(right + i0, drt, m);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return h->hip_fail(e, "lookup D2H");
+  }
+  return MHMKC_OK;
+}
+
+int mhmkc_dbjg_links_device(mhmkc_t h, const uint32_t **d_next, const uint8_t **d_status) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks > 1) return h->fail(MHMKC_EUNSUPPORTED, "dbjg links: single-rank handles only");
+  if (!h->finished) return h->fail(MHMKC_ESTATE, "dbjg links before finish");
+  int rc = h->dbjg_links();
+  if (rc) return rc;
+  const uint32_t *next = h->n_out ? h->d_links.as<uint32_t>() : nullptr;
+  if (d_next) *d_next = next;
+  if (d_status) *d_status = next ? (const uint8_t *)(next + 2 * h->n_out) : nullptr;
+  return MHMKC_OK;
+}
+
+int mhmkc_dbjg_links(mhmkc_t h, uint32_t *next, uint8_t *status) {
+  const uint32_t *dn = nullptr;
+  const uint8_t *ds = nullptr;
+  int rc = mhmkc_dbjg_links_device(h, &dn, &ds);
+  if (rc) return rc;
+  const uint64_t n = h->n_out;
+  if (!n) return MHMKC_OK;
+  hipError_t e = hipSuccess;
+  if (next) e = h->d2h(next, dn, 2 * n * 4);
+  if (e == hipSuccess && status) e = h->d2h(status, ds, 2 * n);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "dbjg links D2H");
+}
+
 int mhmkc_get_stats(mhmkc_t h, mhmkc_stats *s) {
   if (!h || !s) return MHMKC_EINVAL;
   *s = h->st;
@@ -3914,7 +4075,13 @@ int mhmkc_reset(mhmkc_t h) {
   h->partial = false;
   h->n_out = 0;
   h->ord_ready = false;
+  const bool had_query = h->d_qidx.p || h->d_links.p || h->d_qstage.p;
+  h->drop_query();
   memset(&h->st, 0, sizeof h->st);
+  if (had_query) {  // (the query buffers were counted into the finished round's device_bytes: report what is left)
+    h->st.device_bytes = g_dev_live.load();
+    h->st.device_bytes_peak = g_dev_peak.load();
+  }
   if ((e = hipMemsetAsync(h->d_err.p, 0, 16, h->stream)) != hipSuccess) return h->hip_fail(e, "reset");
   return MHMKC_OK;
 }
@@ -3948,6 +4115,7 @@ int mhmkc_debug_set(const char *knob, int64_t value) {
   else if (k == "cb0") g_dbg.cb0[1] = value;
   else if (k == "cb0_2") g_dbg.cb0[2] = value;
   else if (k == "cb0_3") g_dbg.cb0[3] = value;
+  else if (k == "query_slots_log2") g_dbg.query_slots_log2 = value;
   else return MHMKC_EINVAL;
   return MHMKC_OK;
 }

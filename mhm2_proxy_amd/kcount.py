@@ -446,6 +446,77 @@ class KmerCounter:
         return {"keys": ptrs[0].value, "counts": ptrs[1].value, "left": ptrs[2].value, "right": ptrs[3].value,
                 "n_out": int(n.value), "n_longs": self.n_longs}
 
+    # -- queries on the finished table (mhmkc_lookup, mhmkc_dbjg_links)
+    def _query_keys(self, keys) -> np.ndarray:
+        if isinstance(keys, (list, tuple)) and (len(keys) == 0 or isinstance(keys[0], str)):
+            if any(len(s) != self.k for s in keys):
+                raise ValueError(f"every k-mer string must have {self.k} bases")
+            keys = np.array([kmer_from_string(s, self.n_longs) for s in keys], dtype=np.uint64)
+        kk = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.n_longs)
+        return kk
+
+    def lookup(self, keys, canonicalize: bool = False):
+        """KmerDHT::get_local_kmer_counts (canonicalize=False: the key as given) or kmer_exists (canonicalize=True:
+        min(key, revcomp(key))) for a batch of k-mers, answered on the GPU (src/kcount/kmer_dht.cpp:198-219).
+        keys: an (n, n_longs) uint64 array in Kmer::longs layout, or a list of k-mer strings. Returns numpy arrays
+        (rows, counts, left, right): rows[i] is the row of fetch() holding key i or MHMKC_NO_ROW (0xFFFFFFFF),
+        counts / left / right that row's fields (0 on a miss; left / right in the stored, canonical frame)."""
+        kk = self._query_keys(keys)
+        n = kk.shape[0]
+        rows = np.empty(n, dtype=np.uint32)
+        counts = np.empty(n, dtype=np.uint16)
+        left = np.empty(n, dtype=np.uint8)
+        right = np.empty(n, dtype=np.uint8)
+        self._check(N.lib().mhmkc_lookup(self._h, kk.ctypes.data, n, int(bool(canonicalize)), rows.ctypes.data,
+                                         counts.ctypes.data, left.ctypes.data, right.ctypes.data))
+        return rows, counts, left, right
+
+    def synchronize(self) -> None:
+        """Wait for the counter's stream (mhmkc_fetch with no output arrays copies nothing and waits for it)."""
+        self._check(N.lib().mhmkc_fetch(self._h, None, None, None, None))
+
+    def lookup_tensors(self, keys_t, canonicalize: bool = False, sync: bool = True):
+        """lookup() for keys already in HBM: a uint64 / int64 torch tensor of n * n_longs words on the counter's
+        device. Returns torch tensors (rows int32 holding the uint32 bits, so a miss reads -1; counts int16 holding
+        the uint16 bits; left, right uint8) allocated by torch and written on the counter's own stream, which is first
+        ordered after torch's current stream (as add_tensors). With sync=True (default) the call waits for the
+        counter's stream, so the tensors are ready for any stream. With sync=False it returns at once: call
+        synchronize() before reading them (or before freeing keys_t), or create the counter on the torch stream that
+        consumes them (KmerCounter(stream=torch.cuda.current_stream().cuda_stream)), which orders everything."""
+        import torch
+
+        if keys_t.dtype not in (torch.uint64, torch.int64):
+            raise ValueError("keys_t must be a uint64 or int64 tensor")
+        if not keys_t.is_contiguous() or keys_t.numel() % self.n_longs:
+            raise ValueError("keys_t must be contiguous with n * n_longs words")
+        n = keys_t.numel() // self.n_longs
+        dev = keys_t.device
+        rows = torch.empty(n, dtype=torch.int32, device=dev)
+        counts = torch.empty(n, dtype=torch.int16, device=dev)
+        left = torch.empty(n, dtype=torch.uint8, device=dev)
+        right = torch.empty(n, dtype=torch.uint8, device=dev)
+        self._after_torch(keys_t)
+        self._check(N.lib().mhmkc_lookup_device(self._h, keys_t.data_ptr(), n, int(bool(canonicalize)),
+                                                rows.data_ptr(), counts.data_ptr(), left.data_ptr(), right.data_ptr()))
+        if sync:
+            self.synchronize()
+        return rows, counts, left, right
+
+    def dbjg_links(self):
+        """The de Bruijn links of every row (mhmkc_dbjg_links): numpy arrays next[2, n_out] (uint32 rows, MHMKC_NO_ROW:
+        none) and status[2, n_out] (MHMKC_LINK_*), direction 0 = LEFT, 1 = RIGHT, in each row's stored orientation."""
+        n = self.n_out or 0  # (before finish the library refuses the call)
+        nxt = np.empty((2, n), dtype=np.uint32)
+        status = np.empty((2, n), dtype=np.uint8)
+        self._check(N.lib().mhmkc_dbjg_links(self._h, nxt.ctypes.data, status.ctypes.data))
+        return nxt, status
+
+    def dbjg_links_device(self) -> dict:
+        """Device pointers of the link arrays (mhmkc_dbjg_links_device), kept until the next reset / finish."""
+        pn, ps = C.c_void_p(), C.c_void_p()
+        self._check(N.lib().mhmkc_dbjg_links_device(self._h, C.byref(pn), C.byref(ps)))
+        return {"next": pn.value, "status": ps.value, "n_out": self.n_out}
+
     def stats(self) -> dict:
         s = N.MhmkcStats()
         self._check(N.lib().mhmkc_get_stats(self._h, C.byref(s)))
@@ -715,8 +786,27 @@ class KmerDHT:
         return self.get_local_num_kmers()
 
     def get_local_kmer_counts(self, kmer) -> KmerCounts | None:
+        """get_local_kmer_counts (src/kcount/kmer_dht.cpp:198-204): the k-mer as given, no canonicalisation. With a
+        finished counter attached it is one lookup on the GPU (KmerCounter.lookup); only a table without a live counter
+        (closed, or reset since) goes through the local_kmers dict."""
         key = kmer_from_string(kmer) if isinstance(kmer, str) else tuple(int(x) for x in kmer)
+        if self._counter_has_table() and len(key) == self.counter.n_longs:
+            rows, counts, left, right = self.counter.lookup(np.array([key], dtype=np.uint64))
+            if int(rows[0]) == N.MHMKC_NO_ROW:
+                return None
+            return KmerCounts(int(counts[0]), chr(int(left[0])), chr(int(right[0])))
         return self.local_kmers.get(key)
+
+    def _counter_has_table(self) -> bool:
+        c = self.counter
+        return c is not None and getattr(c, "_h", None) is not None and c.n_out is not None and self.table is not None
+
+    def kmer_exists(self, kmer) -> bool:
+        """kmer_exists (src/kcount/kmer_dht.cpp:206-219) for this rank's k-mers: the k-mer is canonicalised, then
+        looked up (KmerCounter.lookup with canonicalize=True)."""
+        key = kmer_from_string(kmer, self.counter.n_longs) if isinstance(kmer, str) else tuple(int(x) for x in kmer)
+        rows = self.counter.lookup(np.array([key], dtype=np.uint64), canonicalize=True)[0]
+        return int(rows[0]) != N.MHMKC_NO_ROW
 
     def get_kmer_target_rank(self, kmer) -> int:
         longs = kmer_from_string(kmer) if isinstance(kmer, str) else kmer

@@ -1,0 +1,49 @@
+"""The query side of the C++ adapter (include/mhmkc_kcount.hpp): KmerDHT::kmer_exists, the batch KmerDHT::lookup over
+mhmkc_lookup and HashTableInserter::dbjg_links, checked by tests/cpp/query_test.cpp against the adapter's own KmerMap."""
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+import mhm2_proxy_amd as m
+from common import synth_set
+
+ROOT = Path(__file__).resolve().parents[1]
+SRC = ROOT / "tests" / "cpp" / "query_test.cpp"
+
+
+def build(tmp: Path) -> Path:
+    if not shutil.which("g++"):
+        pytest.skip("g++ missing")
+    from mhm2_proxy_amd import build as b
+
+    b.build_lib()
+    exe = tmp / "query_test"
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", f"-I{ROOT / 'include'}", str(SRC),
+                    f"-L{ROOT / 'mhm2_proxy_amd'}", "-lmhmkc", "-lz", f"-Wl,-rpath,{ROOT / 'mhm2_proxy_amd'}",
+                    "-o", str(exe)], check=True)
+    return exe
+
+
+def test_query_adapter_compiles_for_every_max_k(tmp_path):
+    """CPU: kmer_exists, lookup and dbjg_links instantiate for MAX_K = 32, 64, 96 and 128 (query_test.cpp's main)."""
+    exe = build(tmp_path)
+    assert subprocess.run([str(exe)], env={"MHMKC_NO_TORCH": "1"}).returncode == 2  # usage: no GPU touched
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [21, 63])
+def test_query_adapter_matches_its_kmermap(k, tmp_path):
+    exe = build(tmp_path)
+    b, o = synth_set(3000, 20000, 5)
+    pr = m.PackedReads.from_arrays(b, o)
+    reads = tmp_path / "reads.txt"
+    with open(reads, "w") as f:
+        for i in range(pr.get_local_num_reads()):
+            _, s, q = pr.get_read(i)
+            f.write(f"{s} {q}\n")
+    out = subprocess.run([str(exe), str(k), str(reads)], capture_output=True, text=True, cwd=tmp_path)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    words = out.stdout.split()
+    assert words[0] == "OK" and int(words[1]) > 1000 and int(words[2]) == 3 * int(words[1])
