@@ -355,6 +355,53 @@ int mhmkc_dbjg_links(mhmkc_t h, uint32_t *next, uint8_t *status);
 /* The same arrays on the device, computed once per finish and kept until the next reset / finish / destroy. */
 int mhmkc_dbjg_links_device(mhmkc_t h, const uint32_t **d_next, const uint8_t **d_status);
 
+/* The uutigs of the finished table, built on the GPU from those links: traverse_debruijn_graph at one rank
+ * (src/dbjg_traversal.cpp:165-289,301-307,404-407,539-541,569-596) without its visited array.
+ *   Ports: row i has the ports (i,0) LEFT and (i,1) RIGHT. An OK port (i,d) leads to row j = next[d][i], where travel
+ *   goes on in direction dc = d ^ rc: it enters j at port (j, dc^1). (i,d) is linked iff it is OK, the port it enters is
+ *   not itself (a hairpin) and that port is OK and enters (i,d); every other port is an end.
+ *   Components: under linked ports the rows whose two extensions are bases form simple paths and simple cycles. A
+ *   component of m rows is one uutig of m + k - 1 bases; its start is its row with the smallest key (Kmer::operator<).
+ *   Layout: in the start's stored orientation, leftwards first: position 0 is the end reached through the start's port
+ *   0; a cycle is opened between the start's port 1 and the row it leads to, which takes position 0 (the start m - 1).
+ *   The row at position p gives base p (its first base as it lies in the contig), the last row its whole k-mer.
+ *   Depth: (the sum of the m counts + the start's count) / (m + 1), the sum in 64 bits, one double division: the host
+ *   walker counts the start in both walks (:224) and divides by len - k + 2.
+ *   Order: contig c is the component with the c-th smallest start, the id traverse_debruijn_graph assigns and the
+ *   order mhmkc_add_ctgs of the next round expects.
+ *   For even k a start that is its own reverse complement and whose port 0 is its non-mutual one comes out on the
+ *   other strand than the host walker's; either strand is the same uutig.
+ * Built once per finish (the index and the links first if needed), kept until the next reset / finish / destroy and
+ * counted in mhmkc_stats.device_bytes[_peak]: 9 bytes per row (the row map), 1 per base, 20 per contig + 8. The
+ * ranking's scratch (128 bytes per row at its peak) is freed before the call returns. Single-rank handles only
+ * (MHMKC_EUNSUPPORTED with n_ranks > 1, checked before the state); before finish: MHMKC_ESTATE; at most 2^32-2 rows. */
+int mhmkc_uutigs(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases);
+/* Host copies (any may be NULL): offsets[n_ctgs + 1] into seqs[n_bases] (ASCII ACGT, the format mhmkc_add_ctgs takes),
+ * depths[n_ctgs], n_kmers[n_ctgs] (m). */
+int mhmkc_uutigs_fetch(mhmkc_t h, uint64_t *offsets, char *seqs, double *depths, uint32_t *n_kmers);
+/* The same arrays on the device (any pointer may be NULL; an empty table still has offsets = {0}). */
+int mhmkc_uutigs_device(mhmkc_t h, const uint64_t **d_offsets, const char **d_seqs, const double **d_depths,
+                        uint64_t *n_ctgs, uint64_t *n_bases);
+/* Where every row lies: row_ctg[n_out] (MHMKC_NO_ROW: in no contig), row_pos[n_out] (its position, 0 .. m-1),
+ * row_rc[n_out] (1: reverse-complemented in its contig; 0 for a start). Host arrays, any may be NULL. */
+int mhmkc_uutig_rows(mhmkc_t h, uint32_t *row_ctg, uint32_t *row_pos, uint8_t *row_rc);
+int mhmkc_uutig_rows_device(mhmkc_t h, const uint32_t **d_row_ctg, const uint32_t **d_row_pos, const uint8_t **d_row_rc);
+
+/* How the last mhmkc_uutigs build went (device events on the handle's stream). */
+#define MHMKC_UUTIG_MAX_ROUNDS 48
+typedef struct {
+  uint64_t n_ctgs, n_bases;
+  uint64_t rounds;        /* pointer-jumping rounds over all ports */
+  uint64_t cycle_ports;   /* ports left on cycles after them (two per cycle row) */
+  uint64_t cycle_rounds;  /* rounds over those ports alone: finding the start, then ranking the opened cycle */
+  uint64_t scratch_bytes; /* the peak of the build's device memory above what stays */
+  uint64_t kept_bytes;    /* what stays: contig arrays and row map */
+  double ms_links;        /* index + links, when this call built them (else 0) */
+  double ms_succ, ms_rank, ms_cycles, ms_table, ms_rows, ms_total; /* ms_total: succ .. rows */
+  double ms_round[MHMKC_UUTIG_MAX_ROUNDS]; /* the first rounds' times, one by one */
+} mhmkc_uutig_info;
+int mhmkc_uutigs_info(mhmkc_t h, mhmkc_uutig_info *info);
+
 /* Host-staged exchange between ranks (instead of RCCL): for n_ranks > 1 with comm_id == NULL, set before
  * the first mhmkc_finish. Every rank's callbacks are called collectively, in the same order on all ranks, with
  * host buffers; a callback returns 0 on success.

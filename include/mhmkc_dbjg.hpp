@@ -137,4 +137,13 @@ void traverse_debruijn_graph(unsigned kmer_len, KmerDHT<MAX_K> &kmer_dht, Contig
   }
 }
 
+// The same traversal on the GPU, from the finished table's de Bruijn links (mhmkc_uutigs): equal
+// uutigs with equal ids and depths, without the KmerMap (kmer_dht needs a counter: not RankInfo::table_only). For even
+// k a uutig whose first k-mer in Kmer order is its own reverse complement may come out as the other strand.
+template <int MAX_K>
+void traverse_debruijn_graph_device(unsigned kmer_len, KmerDHT<MAX_K> &kmer_dht, Contigs &my_uutigs) {
+  if (kmer_len != Kmer<MAX_K>::get_k()) die("traverse_debruijn_graph_device: kmer_len is not the table's k");
+  kmer_dht.inserter().uutigs(my_uutigs);
+}
+
 }  // namespace mhm2

@@ -1019,6 +1019,21 @@ class HashTableInserter {
     status.assign(2 * n, 0);
     check(mhmkc_dbjg_links(h_, next.data(), status.data()), h_, "mhmkc_dbjg_links");
   }
+  // the uutigs of the finished table, built on the GPU from those links (mhmkc_uutigs: traverse_debruijn_graph at one
+  // rank, src/dbjg_traversal.cpp:569-596): Contig{id, seq, depth} in the order of the ids the traversal assigns; only
+  // the contigs come to the host, never the table
+  void uutigs(Contigs &out) {
+    uint64_t n_ctgs = 0, n_bases = 0;
+    check(mhmkc_uutigs(h_, &n_ctgs, &n_bases), h_, "mhmkc_uutigs");
+    std::vector<uint64_t> offs(n_ctgs + 1);
+    std::vector<char> seqs(n_bases);
+    std::vector<double> depths(n_ctgs);
+    check(mhmkc_uutigs_fetch(h_, offs.data(), seqs.data(), depths.data(), nullptr), h_, "mhmkc_uutigs_fetch");
+    out.clear();
+    out.reserve(n_ctgs);
+    for (uint64_t c = 0; c < n_ctgs; c++)
+      out.push_back(Contig{(int64_t)c, std::string(seqs.data() + offs[c], seqs.data() + offs[c + 1]), depths[c]});
+  }
 };
 
 template <int MAX_K>

@@ -50,10 +50,26 @@ ABI_SYMBOLS = [
     "mhmkc_fastq_packed", "mhmkc_fastq_fetch",
     "mhmkc_wait_stream", "mhmkc_set_dmin_thres", "mhmkc_set_transport", "mhmkc_minimizer_hashes",
     "mhmkc_lookup", "mhmkc_lookup_device", "mhmkc_dbjg_links", "mhmkc_dbjg_links_device",
+    "mhmkc_uutigs", "mhmkc_uutigs_fetch", "mhmkc_uutigs_device", "mhmkc_uutig_rows", "mhmkc_uutig_rows_device",
+    "mhmkc_uutigs_info",
 ]
+UUTIG_MAX_ROUNDS = 48
 SYNTH_SYMBOLS = ["mhmkc_synth_config_init", "mhmkc_synth_genome", "mhmkc_synth_reads"]
 # the test-only entry point (include/mhmkc_debug.h)
 DEBUG_SYMBOLS = ["mhmkc_debug_nib_pack", "mhmkc_debug_reset", "mhmkc_debug_set"]
+
+
+class MhmkcUutigInfo(C.Structure):
+    """mhmkc_uutig_info (include/mhmkc.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("n_ctgs", "n_bases", "rounds", "cycle_ports", "cycle_rounds", "scratch_bytes",
+                                          "kept_bytes")] + \
+               [(f, C.c_double) for f in ("ms_links", "ms_succ", "ms_rank", "ms_cycles", "ms_table", "ms_rows",
+                                          "ms_total")] + [("ms_round", C.c_double * UUTIG_MAX_ROUNDS)]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "ms_round"}
+        d["ms_round"] = list(self.ms_round)[:min(int(self.rounds), UUTIG_MAX_ROUNDS)]
+        return d
 
 
 class MhmkcConfig(C.Structure):
@@ -251,6 +267,12 @@ def lib() -> C.CDLL:
     L.mhmkc_lookup_device.argtypes = [VP, VP, U64, I32, VP, VP, VP, VP]
     L.mhmkc_dbjg_links.argtypes = [VP, VP, VP]
     L.mhmkc_dbjg_links_device.argtypes = [VP, P(VP), P(VP)]
+    L.mhmkc_uutigs.argtypes = [VP, P(U64), P(U64)]
+    L.mhmkc_uutigs_fetch.argtypes = [VP, VP, VP, VP, VP]
+    L.mhmkc_uutigs_device.argtypes = [VP, P(VP), P(VP), P(VP), P(U64), P(U64)]
+    L.mhmkc_uutig_rows.argtypes = [VP, VP, VP, VP]
+    L.mhmkc_uutig_rows_device.argtypes = [VP, P(VP), P(VP), P(VP)]
+    L.mhmkc_uutigs_info.argtypes = [VP, P(MhmkcUutigInfo)]
     _lib = L
     return L
 

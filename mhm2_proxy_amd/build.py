@@ -6,6 +6,7 @@
   tools/bin/kmermap_fill            g++: KmerMap fill timing of the C++ adapter from table files (tests, bench.py)
   tools/bin/libmhmkc_handoff.so     g++: the adapter's streamed hand-off (load_ordered) timed in bench.py's process
   tools/bin/libmhmkc_qfind.so       g++: hand-off + KmerMap::find on query keys, timed in tools/query_bench.py's process
+  tools/bin/libmhmkc_uhost.so       g++: hand-off + the host traversal on one thread, timed in tools/uutig_bench.py's process
 
 Incremental: a target is rebuilt only when one of its sources is newer; libmhmkc.so also when the build id it
 carries (the SHA-256 of its sources, mhmkc_build_id) is not the tree's, whatever the file times say.
@@ -29,6 +30,7 @@ SYNTH = PKG / "libmhmkc_synth.so"
 ORACLE = ROOT / "oracle" / "liboracle.so"
 
 LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kcount_owner.hip", CSRC / "kcount_query.hip",
+               CSRC / "kcount_uutig.hip",
                CSRC / "fastq.hip",
                CSRC / "mhmkc_host.cpp"]
 LIB_DEPS = LIB_SOURCES + [CSRC / "kcount_launch.hpp", CSRC / "kmer_ops.hpp", ROOT / "include" / "mhmkc.h"]
@@ -40,6 +42,10 @@ HANDOFF_DEPS = [ROOT / "tools" / "cpp" / "handoff.cpp", ROOT / "include" / "mhmk
 # tools/query_bench.py's comparison route: the hand-off into a KmerMap, then KmerMap::find on the query keys
 QFIND = ROOT / "tools" / "bin" / "libmhmkc_qfind.so"
 QFIND_DEPS = [ROOT / "tools" / "cpp" / "query_find.cpp", ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]
+# tools/uutig_bench.py's comparison route: the hand-off into a KmerMap, then the host traversal on one thread
+UHOST = ROOT / "tools" / "bin" / "libmhmkc_uhost.so"
+UHOST_DEPS = [ROOT / "tools" / "cpp" / "uutig_host.cpp", ROOT / "include" / "mhmkc_dbjg.hpp",
+              ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]
 # test infrastructure: the restated traversal over a given table (the multi-rank multi-k chain, tests/test_c5_scale.py)
 DBJG = ROOT / "tools" / "bin" / "libmhmkc_dbjg.so"
 DBJG_DEPS = [ROOT / "tools" / "cpp" / "dbjg_lib.cpp", ROOT / "include" / "mhmkc_dbjg.hpp",
@@ -179,6 +185,16 @@ def build_qfind(force: bool = False) -> Path:
     return QFIND
 
 
+def build_uhost(force: bool = False) -> Path:
+    if force or _stale(UHOST, UHOST_DEPS + [LIB]):
+        UHOST.parent.mkdir(parents=True, exist_ok=True)
+        tmp = UHOST.with_suffix(".tmp")
+        _run(["g++", "-O2", "-std=c++17", "-pthread", "-fPIC", "-shared", "-I", ROOT / "include", UHOST_DEPS[0], "-L",
+              PKG, "-lmhmkc", "-lz", "-Wl,-rpath,$ORIGIN/../../mhm2_proxy_amd", "-o", tmp])
+        tmp.replace(UHOST)
+    return UHOST
+
+
 def build_all(force: bool = False) -> None:
     build_lib(force)
     build_synth(force)
@@ -187,6 +203,7 @@ def build_all(force: bool = False) -> None:
     build_handoff(force)
     build_dbjg(force)
     build_qfind(force)
+    build_uhost(force)
 
 
 if __name__ == "__main__":

@@ -431,4 +431,38 @@ hipError_t launch_query_lookup(const uint64_t *q, uint64_t n, bool canonicalize,
 hipError_t launch_dbjg_links(const OutRows &t, uint64_t n, int k, int nl, int nlo, const QueryIndex &ix, uint32_t *next,
                              uint8_t *status, hipStream_t s);
 
+// The uutigs of the table from those links (kcount_uutig.hip). Port 2 * row + d; a port's ranking state:
+// link = the port reached (bits 0-39) | the round that wrote it (bits 48-55) | done (bit 63: the port is the chain's end
+// port), dist / sum / minw0, minrow = the rows passed, their counts, the smallest key among them.
+struct alignas(32) UutigPort {
+  uint64_t link, sum, minw0;
+  uint32_t dist, minrow;
+};
+// the first state of all 2 n ports (list == null, n_items = 2 n) or of the listed ones; cut: the listed ports' cycles
+// are opened at the start their state in cut names
+hipError_t launch_uutig_init(const OutRows &t, uint64_t n, int nlo, const uint32_t *next, const uint8_t *status,
+                             const uint64_t *list, uint64_t n_items, const UutigPort *cut, uint32_t round, UutigPort *st,
+                             hipStream_t s);
+// one pointer-jumping round src -> dst; *active += the ports that are not done after it
+hipError_t launch_uutig_jump(const UutigPort *src, UutigPort *dst, uint64_t n, const uint64_t *list, uint64_t n_items,
+                             const uint64_t *keys, int nl, int nlo, uint32_t round, unsigned long long *active,
+                             hipStream_t s);
+// the ports that are not done, appended to list (at most cap)
+hipError_t launch_uutig_active(const UutigPort *st, uint64_t n, uint64_t *list, uint64_t cap, unsigned long long *n_list,
+                               hipStream_t s);
+// row_pos[i] = the start row of row i's component, row_ctg = 0xFFFFFFFF, the start rows appended to starts [n]
+hipError_t launch_uutig_starts(const OutRows &t, uint64_t n, int nl, int nlo, const UutigPort *st, uint32_t *row_ctg,
+                               uint32_t *row_pos, uint8_t *row_rc, uint32_t *starts, unsigned long long *n_starts,
+                               hipStream_t s);
+size_t uutig_table_scratch_bytes(uint64_t n_ctgs);
+// starts sorted by key; n_kmers / depths [n_ctgs], offsets [n_ctgs + 1], row_ctg of the start rows
+hipError_t launch_uutig_table(const OutRows &t, uint64_t n, int k, int nl, int nlo, const UutigPort *st, uint32_t *starts,
+                              uint64_t n_ctgs, void *scratch, size_t scratch_bytes, uint32_t *row_ctg, uint32_t *n_kmers,
+                              double *depths, uint64_t *offsets, hipStream_t s);
+hipError_t launch_uutig_place(const OutRows &t, uint64_t n, const UutigPort *st, uint32_t *row_ctg, uint32_t *row_pos,
+                              uint8_t *row_rc, hipStream_t s);
+hipError_t launch_uutig_bases(const OutRows &t, uint64_t n, int k, int nl, int nlo, const uint32_t *row_ctg,
+                              const uint32_t *row_pos, const uint8_t *row_rc, const uint64_t *offsets,
+                              const uint32_t *n_kmers, uint64_t n_ctgs, uint64_t n_bases, char *seqs, hipStream_t s);
+
 }  // namespace mhm

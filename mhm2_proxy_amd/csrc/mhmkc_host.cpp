@@ -481,12 +481,37 @@ struct mhmkc {
   int lookup_device(const uint64_t *d_keys, uint64_t n, int canonicalize, uint32_t *d_rows, uint16_t *d_counts,
                     char *d_left, char *d_right);
   int dbjg_links();
+  // the uutigs built from the links (kcount_uutig.hip). Kept: d_uctg (offsets u64 [n_ctgs + 1], depths
+  // f64 [n_ctgs], n_kmers u32 [n_ctgs]), d_useq (the bases), d_urows (row_ctg u32, row_pos u32, row_rc u8, [n_out] each);
+  // the ranking's scratch (two port-state buffers, the cycle ports' list, a counter, the contig table's sort scratch) is
+  // released before uutigs() returns. Dropped with the other query buffers.
+  DevBuf d_uctg, d_useq, d_urows, d_ua, d_ub, d_ulist, d_ucnt, d_utbl;
+  bool uutigs_ready = false;
+  uint64_t u_nctgs = 0, u_nbases = 0;
+  mhmkc_uutig_info uinfo{};
+  int uutigs();
+  int uutigs_build(std::vector<hipEvent_t> &evs);
+  void drop_uutig_scratch() {
+    d_ua.release();
+    d_ub.release();
+    d_ulist.release();
+    d_ucnt.release();
+    d_utbl.release();
+  }
+  const uint64_t *u_offsets() const { return d_uctg.as<uint64_t>(); }
+  const double *u_depths() const { return (const double *)(d_uctg.as<char>() + align_up((u_nctgs + 1) * 8, 256)); }
+  const uint32_t *u_nkmers() const { return (const uint32_t *)((const char *)u_depths() + align_up(u_nctgs * 8 + 8, 256)); }
   void drop_query() {
     d_qidx.release();
     d_links.release();
     d_qstage.release();
+    d_uctg.release();
+    d_useq.release();
+    d_urows.release();
+    drop_uutig_scratch();
     qidx = mhm::QueryIndex{};
-    qidx_ready = links_ready = false;
+    qidx_ready = links_ready = uutigs_ready = false;
+    u_nctgs = u_nbases = 0;
   }
   DevBuf d_spill;  // k_count: the deferred records of cold sweeps, mhm::SPILL_RECORDS per persistent workgroup
   DevBuf d_cfit;   // capped fine layout: per coarse bucket of the pass its first record and fine-bucket capacity
@@ -4038,6 +4063,275 @@ int mhmkc_dbjg_links(mhmkc_t h, uint32_t *next, uint8_t *status) {
   return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "dbjg links D2H");
 }
 
+// The uutigs of the table from its links (traverse_debruijn_graph at one rank, src/dbjg_traversal.cpp:165-289,301-307,
+// 404-407,539-541,569-596): port successors, list ranking by pointer jumping, the cycles opened at their start and
+// ranked again, the contig table sorted by start key, the row map and the bases. evs: the stage marks of this build.
+int mhmkc::uutigs_build(std::vector<hipEvent_t> &evs) {
+  const uint64_t n = n_out;
+  hipError_t e = hipSuccess;
+  auto mark = [&]() -> int {
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return -1;
+    (void)hipEventRecord(ev, stream);
+    evs.push_back(ev);
+    return (int)evs.size() - 1;
+  };
+  auto ms = [&](int a, int b) -> double {
+    float f = 0;
+    if (a < 0 || b < 0 || hipEventElapsedTime(&f, evs[(size_t)a], evs[(size_t)b]) != hipSuccess) return 0;
+    return (double)f;
+  };
+  const bool had_links = links_ready;
+  const int t_l = mark();
+  int rc = dbjg_links();
+  if (rc) return rc;
+  const int t_l1 = mark();
+  u_nctgs = u_nbases = 0;
+  if (!n) {  // an empty table: no kernel runs, offsets = {0}
+    if ((e = grow(d_uctg, 1024)) != hipSuccess || (e = hipMemsetAsync(d_uctg.p, 0, 8, stream)) != hipSuccess)
+      return hip_fail(e, "uutigs");
+    uinfo.kept_bytes = d_uctg.cap;
+    return MHMKC_OK;
+  }
+  const uint32_t *next = d_links.as<uint32_t>();
+  const uint8_t *status = (const uint8_t *)(next + 2 * n);
+  const size_t rows_b = align_up(n * 4, 256);
+  if ((e = grow(d_urows, 2 * rows_b + n + 64)) != hipSuccess || (e = grow(d_ua, 2 * n * sizeof(mhm::UutigPort))) != hipSuccess ||
+      (e = grow(d_ub, 2 * n * sizeof(mhm::UutigPort))) != hipSuccess || (e = grow(d_ucnt, 64)) != hipSuccess)
+    return e == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "uutigs: ranking scratch for %llu rows", (unsigned long long)n)
+                                    : hip_fail(e, "uutigs");
+  uint32_t *row_ctg = d_urows.as<uint32_t>();
+  uint32_t *row_pos = (uint32_t *)(d_urows.as<char>() + rows_b);
+  uint8_t *row_rc = (uint8_t *)(d_urows.as<char>() + 2 * rows_b);
+  mhm::UutigPort *F = d_ua.as<mhm::UutigPort>(), *G = d_ub.as<mhm::UutigPort>();
+  unsigned long long *cnt = d_ucnt.as<unsigned long long>();
+  const uint64_t *keys = d_out_keys.as<uint64_t>();
+  auto count_back = [&](uint64_t &v) -> hipError_t {
+    unsigned long long x = 0;
+    hipError_t r = hipMemcpyAsync(&x, cnt, 8, hipMemcpyDeviceToHost, stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(stream);
+    v = x;
+    return r;
+  };
+
+  // stage 1: the port successors (the stage times start here, after the scratch is allocated)
+  const int t0 = mark();
+  uint32_t round = 0;
+  if ((e = mhm::launch_uutig_init(out_rows(), n, nlo, next, status, nullptr, 2 * n, nullptr, round, F, stream)) != hipSuccess)
+    return hip_fail(e, "uutig ports");
+  const int t1 = mark();
+
+  // stage 2: pointer jumping. After round r a port is done iff its end is at most 2^r - 1 ports away, so as long as a
+  // path is unfinished the count of ports under way falls; once it stands still, what is left lies on cycles
+  int max_rounds = 1;
+  while ((1ull << max_rounds) < 2 * n) max_rounds++;
+  max_rounds++;
+  uint64_t active = 0, prev = ~0ull;
+  int rounds = 0, t_prev = t1;
+  while (rounds < max_rounds) {
+    round++;
+    if ((e = hipMemsetAsync(cnt, 0, 8, stream)) != hipSuccess ||
+        (e = mhm::launch_uutig_jump(F, G, n, nullptr, 2 * n, keys, nl, nlo, round, cnt, stream)) != hipSuccess)
+      return hip_fail(e, "uutig ranking");
+    const int t = mark();
+    if ((e = count_back(active)) != hipSuccess) return hip_fail(e, "uutig ranking");
+    if (rounds < MHMKC_UUTIG_MAX_ROUNDS) uinfo.ms_round[rounds] = ms(t_prev, t);
+    t_prev = t;
+    rounds++;
+    std::swap(F, G);
+    if (!active || active == prev) break;
+    prev = active;
+  }
+  uinfo.rounds = (uint64_t)rounds;
+  const int t2 = mark();
+
+  // stage 3: the cycles. More rounds over their ports alone until every port has seen its whole cycle (2^rounds >= n)
+  // and so knows its start; the cycle is opened there and ranked as a path
+  if (active) {
+    uinfo.cycle_ports = active;
+    const uint64_t n_list = active;
+    if ((e = grow(d_ulist, n_list * 8)) != hipSuccess) return hip_fail(e, "uutig cycles");
+    uint64_t *list = d_ulist.as<uint64_t>();
+    if ((e = hipMemsetAsync(cnt, 0, 8, stream)) != hipSuccess ||
+        (e = mhm::launch_uutig_active(F, n, list, n_list, cnt, stream)) != hipSuccess)
+      return hip_fail(e, "uutig cycles");
+    int extra = std::max(0, max_rounds - rounds);
+    extra += extra & 1;  // an even number: the last states are in F again, where the paths' are
+    for (int x = 0; x < extra; x++) {
+      round++;
+      if ((e = mhm::launch_uutig_jump(F, G, n, list, n_list, keys, nl, nlo, round, cnt, stream)) != hipSuccess)
+        return hip_fail(e, "uutig cycles");
+      std::swap(F, G);
+      uinfo.cycle_rounds++;
+    }
+    round++;
+    if ((e = mhm::launch_uutig_init(out_rows(), n, nlo, next, status, list, n_list, F, round, F, stream)) != hipSuccess)
+      return hip_fail(e, "uutig cycles");
+    mhm::UutigPort *const F0 = F;
+    uint64_t left = n_list;
+    for (int x = 0; left && x <= max_rounds; x++) {
+      round++;
+      if ((e = hipMemsetAsync(cnt, 0, 8, stream)) != hipSuccess ||
+          (e = mhm::launch_uutig_jump(F, G, n, list, n_list, keys, nl, nlo, round, cnt, stream)) != hipSuccess ||
+          (e = count_back(left)) != hipSuccess)
+        return hip_fail(e, "uutig cycles");
+      std::swap(F, G);
+      uinfo.cycle_rounds++;
+    }
+    if (left) return fail(MHMKC_EHIP, "uutigs: %llu ports of opened cycles never reached an end", (unsigned long long)left);
+    if (F != F0) {  // one more round copies the ports that were done last into the paths' buffer
+      round++;
+      if ((e = mhm::launch_uutig_jump(F, G, n, list, n_list, keys, nl, nlo, round, cnt, stream)) != hipSuccess)
+        return hip_fail(e, "uutig cycles");
+      std::swap(F, G);
+      uinfo.cycle_rounds++;
+    }
+  }
+  const int t3 = mark();
+
+  // stage 4: the contig table (G is free now: it takes the unsorted starts)
+  uint32_t *starts = (uint32_t *)G;
+  uint64_t n_ctgs = 0, n_bases = 0;
+  if ((e = hipMemsetAsync(cnt, 0, 8, stream)) != hipSuccess ||
+      (e = mhm::launch_uutig_starts(out_rows(), n, nl, nlo, F, row_ctg, row_pos, row_rc, starts, cnt, stream)) != hipSuccess ||
+      (e = count_back(n_ctgs)) != hipSuccess)
+    return hip_fail(e, "uutig starts");
+  if (n_ctgs > n) return fail(MHMKC_EHIP, "uutigs: %llu starts in %llu rows", (unsigned long long)n_ctgs, (unsigned long long)n);
+  const size_t tbl_b = mhm::uutig_table_scratch_bytes(n_ctgs);
+  const size_t off_b = align_up((n_ctgs + 1) * 8, 256), dep_b = align_up(n_ctgs * 8 + 8, 256);
+  if ((e = grow(d_utbl, tbl_b)) != hipSuccess || (e = grow(d_uctg, off_b + dep_b + n_ctgs * 4 + 64)) != hipSuccess)
+    return hip_fail(e, "uutig table");
+  u_nctgs = n_ctgs;
+  uint64_t *offsets = d_uctg.as<uint64_t>();
+  double *depths = (double *)u_depths();
+  uint32_t *n_kmers = (uint32_t *)u_nkmers();
+  if ((e = mhm::launch_uutig_table(out_rows(), n, k, nl, nlo, F, starts, n_ctgs, d_utbl.p, tbl_b, row_ctg, n_kmers, depths,
+                                   offsets, stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&n_bases, offsets + n_ctgs, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess)
+    return hip_fail(e, "uutig table");
+  if (n_bases && (e = grow(d_useq, n_bases)) != hipSuccess)
+    return e == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "uutigs: %llu bases", (unsigned long long)n_bases)
+                                    : hip_fail(e, "uutig bases");
+  u_nbases = n_bases;
+  const int t4 = mark();
+
+  // stage 5: the row map and the bases
+  if ((e = mhm::launch_uutig_place(out_rows(), n, F, row_ctg, row_pos, row_rc, stream)) != hipSuccess ||
+      (e = mhm::launch_uutig_bases(out_rows(), n, k, nl, nlo, row_ctg, row_pos, row_rc, offsets, n_kmers, n_ctgs, n_bases,
+                                   d_useq.as<char>(), stream)) != hipSuccess)
+    return hip_fail(e, "uutig rows");
+  const int t5 = mark();
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(e, "uutigs");
+  uinfo.n_ctgs = n_ctgs;
+  uinfo.n_bases = n_bases;
+  uinfo.ms_links = had_links ? 0 : ms(t_l, t_l1);
+  uinfo.ms_succ = ms(t0, t1);
+  uinfo.ms_rank = ms(t1, t2);
+  uinfo.ms_cycles = ms(t2, t3);
+  uinfo.ms_table = ms(t3, t4);
+  uinfo.ms_rows = ms(t4, t5);
+  uinfo.ms_total = ms(t0, t5);
+  uinfo.scratch_bytes = d_ua.cap + d_ub.cap + d_ucnt.cap + d_ulist.cap + d_utbl.cap;
+  uinfo.kept_bytes = d_uctg.cap + d_useq.cap + d_urows.cap;
+  return MHMKC_OK;
+}
+
+int mhmkc::uutigs() {
+  if (uutigs_ready) return MHMKC_OK;
+  if (n_out >= 0xffffffffull) return fail(MHMKC_EUNSUPPORTED, "table queries: at most 2^32-2 rows");
+  uinfo = mhmkc_uutig_info{};
+  std::vector<hipEvent_t> evs;
+  const int rc = uutigs_build(evs);
+  if (rc) (void)hipStreamSynchronize(stream);
+  for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+  drop_uutig_scratch();
+  if (rc) {
+    d_uctg.release();
+    d_useq.release();
+    d_urows.release();
+    u_nctgs = u_nbases = 0;
+  } else {
+    uutigs_ready = true;
+  }
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return rc;
+}
+
+static int uutigs_need(mhmkc_t h) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks > 1) return h->fail(MHMKC_EUNSUPPORTED, "uutigs: single-rank handles only");
+  if (!h->finished) return h->fail(MHMKC_ESTATE, "uutigs before finish");
+  return h->uutigs();
+}
+
+int mhmkc_uutigs(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases) {
+  int rc = uutigs_need(h);
+  if (rc) return rc;
+  if (n_ctgs) *n_ctgs = h->u_nctgs;
+  if (n_bases) *n_bases = h->u_nbases;
+  return MHMKC_OK;
+}
+
+int mhmkc_uutigs_device(mhmkc_t h, const uint64_t **d_offsets, const char **d_seqs, const double **d_depths,
+                        uint64_t *n_ctgs, uint64_t *n_bases) {
+  int rc = uutigs_need(h);
+  if (rc) return rc;
+  if (d_offsets) *d_offsets = h->u_offsets();
+  if (d_seqs) *d_seqs = h->u_nbases ? h->d_useq.as<char>() : nullptr;
+  if (d_depths) *d_depths = h->u_nctgs ? h->u_depths() : nullptr;
+  if (n_ctgs) *n_ctgs = h->u_nctgs;
+  if (n_bases) *n_bases = h->u_nbases;
+  return MHMKC_OK;
+}
+
+int mhmkc_uutigs_fetch(mhmkc_t h, uint64_t *offsets, char *seqs, double *depths, uint32_t *n_kmers) {
+  int rc = uutigs_need(h);
+  if (rc) return rc;
+  const uint64_t nc = h->u_nctgs, nb = h->u_nbases;
+  hipError_t e = hipSuccess;
+  if (offsets) e = h->d2h(offsets, h->u_offsets(), (nc + 1) * 8);
+  if (e == hipSuccess && seqs && nb) e = h->d2h(seqs, h->d_useq.p, nb);
+  if (e == hipSuccess && depths && nc) e = h->d2h(depths, h->u_depths(), nc * 8);
+  if (e == hipSuccess && n_kmers && nc) e = h->d2h(n_kmers, h->u_nkmers(), nc * 4);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "uutigs D2H");
+}
+
+int mhmkc_uutig_rows_device(mhmkc_t h, const uint32_t **d_row_ctg, const uint32_t **d_row_pos, const uint8_t **d_row_rc) {
+  int rc = uutigs_need(h);
+  if (rc) return rc;
+  const uint64_t n = h->n_out;
+  const size_t rows_b = align_up(n * 4, 256);
+  const char *base = n ? h->d_urows.as<char>() : nullptr;
+  if (d_row_ctg) *d_row_ctg = (const uint32_t *)base;
+  if (d_row_pos) *d_row_pos = base ? (const uint32_t *)(base + rows_b) : nullptr;
+  if (d_row_rc) *d_row_rc = base ? (const uint8_t *)(base + 2 * rows_b) : nullptr;
+  return MHMKC_OK;
+}
+
+int mhmkc_uutig_rows(mhmkc_t h, uint32_t *row_ctg, uint32_t *row_pos, uint8_t *row_rc) {
+  const uint32_t *dc = nullptr, *dp = nullptr;
+  const uint8_t *dr = nullptr;
+  int rc = mhmkc_uutig_rows_device(h, &dc, &dp, &dr);
+  if (rc) return rc;
+  const uint64_t n = h->n_out;
+  if (!n) return MHMKC_OK;
+  hipError_t e = hipSuccess;
+  if (row_ctg) e = h->d2h(row_ctg, dc, n * 4);
+  if (e == hipSuccess && row_pos) e = h->d2h(row_pos, dp, n * 4);
+  if (e == hipSuccess && row_rc) e = h->d2h(row_rc, dr, n);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "uutig rows D2H");
+}
+
+int mhmkc_uutigs_info(mhmkc_t h, mhmkc_uutig_info *info) {
+  if (!h || !info) return MHMKC_EINVAL;
+  *info = h->uinfo;
+  return MHMKC_OK;
+}
+
 int mhmkc_get_stats(mhmkc_t h, mhmkc_stats *s) {
   if (!h || !s) return MHMKC_EINVAL;
   *s = h->st;
@@ -4075,7 +4369,7 @@ int mhmkc_reset(mhmkc_t h) {
   h->partial = false;
   h->n_out = 0;
   h->ord_ready = false;
-  const bool had_query = h->d_qidx.p || h->d_links.p || h->d_qstage.p;
+  const bool had_query = h->d_qidx.p || h->d_links.p || h->d_qstage.p || h->d_uctg.p || h->d_urows.p || h->d_useq.p;
   h->drop_query();
   memset(&h->st, 0, sizeof h->st);
   if (had_query) {  // (the query buffers were counted into the finished round's device_bytes: report what is left)

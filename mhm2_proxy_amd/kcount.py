@@ -517,6 +517,57 @@ class KmerCounter:
         self._check(N.lib().mhmkc_dbjg_links_device(self._h, C.byref(pn), C.byref(ps)))
         return {"next": pn.value, "status": ps.value, "n_out": self.n_out}
 
+    # -- the uutigs of the finished table (mhmkc_uutigs)
+    def uutigs(self):
+        """The round's uutigs, built on the GPU from the de Bruijn links (mhmkc_uutigs; traverse_debruijn_graph at one
+        rank, src/dbjg_traversal.cpp:404-407,539-596): numpy arrays (offsets uint64 [n_ctgs + 1], seqs uint8 [n_bases]
+        holding ASCII ACGT, depths float64 [n_ctgs], n_kmers uint32 [n_ctgs]); contig c is seqs[offsets[c]:offsets[c+1]],
+        in the order of the contigs' smallest k-mers (the ids the reference assigns)."""
+        nc, nb = C.c_uint64(), C.c_uint64()
+        self._check(N.lib().mhmkc_uutigs(self._h, C.byref(nc), C.byref(nb)))
+        offsets = np.empty(nc.value + 1, dtype=np.uint64)
+        seqs = np.empty(nb.value, dtype=np.uint8)
+        depths = np.empty(nc.value, dtype=np.float64)
+        n_kmers = np.empty(nc.value, dtype=np.uint32)
+        self._check(N.lib().mhmkc_uutigs_fetch(self._h, offsets.ctypes.data, seqs.ctypes.data, depths.ctypes.data,
+                                               n_kmers.ctypes.data))
+        return offsets, seqs, depths, n_kmers
+
+    def uutig_rows(self):
+        """Where every row of fetch() lies (mhmkc_uutig_rows): numpy arrays row_ctg uint32 (MHMKC_NO_ROW: in no contig),
+        row_pos uint32, row_rc uint8 (1: reverse-complemented in its contig), n_out entries each."""
+        n = self.n_out or 0  # (before finish the library refuses the call)
+        row_ctg = np.empty(n, dtype=np.uint32)
+        row_pos = np.empty(n, dtype=np.uint32)
+        row_rc = np.empty(n, dtype=np.uint8)
+        self._check(N.lib().mhmkc_uutig_rows(self._h, row_ctg.ctypes.data, row_pos.ctypes.data, row_rc.ctypes.data))
+        return row_ctg, row_pos, row_rc
+
+    def uutigs_device(self) -> dict:
+        """Device pointers of the contig arrays and the row map (mhmkc_uutigs_device, mhmkc_uutig_rows_device), kept
+        until the next reset / finish."""
+        po, ps, pd = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nc, nb = C.c_uint64(), C.c_uint64()
+        self._check(N.lib().mhmkc_uutigs_device(self._h, C.byref(po), C.byref(ps), C.byref(pd), C.byref(nc), C.byref(nb)))
+        rc_, rp, rr = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(N.lib().mhmkc_uutig_rows_device(self._h, C.byref(rc_), C.byref(rp), C.byref(rr)))
+        return {"offsets": po.value, "seqs": ps.value, "depths": pd.value, "n_ctgs": int(nc.value),
+                "n_bases": int(nb.value), "row_ctg": rc_.value, "row_pos": rp.value, "row_rc": rr.value,
+                "n_out": self.n_out}
+
+    def uutig_strings(self):
+        """(list of contig strings, depths float64) in contig order, ready for the next round's add_ctgs (which takes
+        Contig::get_uint16_t_depth() of each depth, src/contigs.hpp:65: np.minimum(depths, 65535).astype(np.uint16))."""
+        offsets, seqs, depths, _ = self.uutigs()
+        blob = seqs.tobytes().decode("ascii")
+        return [blob[int(offsets[c]):int(offsets[c + 1])] for c in range(len(depths))], depths
+
+    def uutigs_info(self) -> dict:
+        """Rounds, stage times (device events) and memory of the last uutigs build (mhmkc_uutigs_info)."""
+        info = N.MhmkcUutigInfo()
+        self._check(N.lib().mhmkc_uutigs_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def stats(self) -> dict:
         s = N.MhmkcStats()
         self._check(N.lib().mhmkc_get_stats(self._h, C.byref(s)))
