@@ -37,7 +37,10 @@ extern "C" {
  *   cb0, cb0_2, cb0_3  coarse bits for one-, two-, three/four-word keys (0: 8, 8, 7)
  *   query_slots_log2   the query index (mhmkc_lookup, mhmkc_dbjg_links) gets exactly 2^v slots (0: the smallest power
  *                 of two >= 2 n_out); the query fails with MHMKC_EINVAL if 2^v <= n_out. A load near 1 exercises long
- *                 probe chains and the wrap past the last slot */
+ *                 probe chains and the wrap past the last slot
+ *   query_grid    at most v workgroups for every kernel of the queries and the uutigs (kcount_query.hip,
+ *                 kcount_uutig.hip; the library sorts and scans keep their own grids), so that their grid-stride loops
+ *                 run more than once per thread on a small table (0: the kernels' own grids) */
 int mhmkc_debug_set(const char *knob, int64_t value);
 /* Every knob back to its default. */
 void mhmkc_debug_reset(void);

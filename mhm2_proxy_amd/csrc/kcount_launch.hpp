@@ -419,6 +419,14 @@ struct QueryIndex {
   int shift;        // 64 - log2(capacity)
 };
 hipError_t preload_query_kernels();
+// Workgroups of a grid-stride launch over n items, 256 threads each, of kcount_query.hip and kcount_uutig.hip. The test
+// knob query_grid (include/mhmkc_debug.h) caps them at query_grid_cap, so that the loops stride on a small table; 0, the
+// product's value: the kernels' own grids.
+inline unsigned query_grid_cap = 0;
+inline unsigned query_grid_for(uint64_t n) {
+  const uint64_t g = n + 255 < 16384ull * 256 ? (n + 255) / 256 : 16384;
+  return (unsigned)(g < 1 ? 1 : (query_grid_cap && query_grid_cap < g ? query_grid_cap : g));
+}
 // nl = k/32 + 1 key words (1..4) of the nlo words per row / query
 hipError_t launch_query_build(const uint64_t *keys, uint64_t n, int nl, int nlo, const QueryIndex &ix, hipStream_t s);
 // rows[i] = the row of query i (0xFFFFFFFF: not in the table), counts / left / right its fields (0 on a miss); any

@@ -25,7 +25,7 @@ constexpr int Q_THREADS = 256;
 constexpr unsigned long long SLOT_EMPTY = ~0ull;
 constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
 
-inline unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(16384, (n + 255) / 256)); }
+inline unsigned grid_for(uint64_t n) { return query_grid_for(n); }
 
 // mhmkc_map_hash of a key whose first NL words are w and whose other nlo - NL words are zero (the output rows'
 // layout for n_longs > k/32 + 1)

@@ -33,7 +33,7 @@ constexpr uint64_t PORT_MASK = (1ull << 40) - 1;
 constexpr uint64_t DONE = 1ull << 63;
 constexpr int ROUND_SHIFT = 48;
 
-inline unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(16384, (n + 255) / 256)); }
+inline unsigned grid_for(uint64_t n) { return query_grid_for(n); }
 
 __device__ __forceinline__ bool is_base(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 

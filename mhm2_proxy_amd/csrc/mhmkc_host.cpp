@@ -67,6 +67,8 @@ struct DebugKnobs {
                               // bytes, -1 1 with >= 4 host threads, else 0
   int64_t cb0[4] = {0, 0, 0, 0};  // coarse bits by key words (0: the default)
   int64_t query_slots_log2 = 0;   // slots of the query index, as a power of two (0: the smallest one >= 2 n_out)
+  // query_grid, the most workgroups of every query / uutig kernel (0: the kernels' own grids), lives where the launches
+  // of kcount_query.hip and kcount_uutig.hip read it: mhm::query_grid_cap (kcount_launch.hpp)
 };
 DebugKnobs g_dbg;
 
@@ -4410,11 +4412,15 @@ int mhmkc_debug_set(const char *knob, int64_t value) {
   else if (k == "cb0_2") g_dbg.cb0[2] = value;
   else if (k == "cb0_3") g_dbg.cb0[3] = value;
   else if (k == "query_slots_log2") g_dbg.query_slots_log2 = value;
+  else if (k == "query_grid") mhm::query_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else return MHMKC_EINVAL;
   return MHMKC_OK;
 }
 
-void mhmkc_debug_reset(void) { g_dbg = DebugKnobs(); }
+void mhmkc_debug_reset(void) {
+  g_dbg = DebugKnobs();
+  mhm::query_grid_cap = 0;
+}
 
 int mhmkc_debug_nib_pack(const uint8_t *src, uint64_t n, uint8_t *dst, int qcut, int mode) {
   if ((!src || !dst) && n) return MHMKC_EINVAL;

@@ -18,6 +18,7 @@ import pytest
 import mhm2_proxy_amd as m
 from common import edge_case_set, hot_set, oracle_table, synth_set
 from query_lib import CONFLICT, DEADEND, FORK, NO_ROW, OK, RC, WHY, links_ref, walk_links
+from uutig_lib import palindrome_set
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -98,10 +99,19 @@ class DeviceArray:
 
 
 CASES = [("synth", k) for k in (21, 22, 33, 63, 77, 99, 127)] + [("edge", 21), ("hot", 21)]
+# key-word boundaries (31 bases in one word; 1 and 31 bases in the third word; 1 in the fourth) on a small read set, and
+# even k above 32 on the palindromes, whose centre row is its own reverse complement: a multi-word key whose neighbour in
+# both directions is the same row
+BOUNDARY = [("small", k) for k in (31, 65, 95, 97)] + [(f"pal{w}", k) for k in (34, 66, 98) for w in ("", "+")]
+CASES += BOUNDARY
+STRIDED = [("synth", 21), ("synth", 77)]
 
 
-def case_reads(setname):
-    return {"synth": lambda: synth_set(3000, 20000, 5), "edge": edge_case_set, "hot": hot_set}[setname]()
+def case_reads(setname, k=0):
+    if setname.startswith("pal"):
+        return palindrome_set(k, setname.endswith("+"), read_len=160)
+    return {"synth": lambda: synth_set(3000, 20000, 5), "small": lambda: synth_set(600, 3000, 7), "edge": edge_case_set,
+            "hot": hot_set}[setname]()
 
 
 @pytest.mark.gpu
@@ -109,12 +119,17 @@ def case_reads(setname):
 def test_links_equal_the_restated_rules(setname, k, knob):
     import torch
 
-    b, o = case_reads(setname)
+    b, o = case_reads(setname, k)
     c, t = gpu_table(b, o, k)
     try:
         n = len(t)
         exp = links_ref(t)[:2]
         assert_links(c.dbjg_links(), exp, f"{setname} k={k}")
+        if setname == "small":  # links that are followed, onto both strands
+            assert n > 1000 and {OK, OK | RC} <= {int(x) for x in np.unique(exp[1])}
+        if setname.startswith("pal"):  # exactly one row, the genome's centre, is its own reverse complement
+            comp = str.maketrans("ACGT", "TGCA")
+            assert sum(s == s[::-1].translate(comp) for s in m.keys_to_strings(t.keys, k)) == 1
         # the device arrays hold the same
         dev = c.dbjg_links_device()
         assert dev["n_out"] == n
@@ -132,6 +147,38 @@ def test_links_equal_the_restated_rules(setname, k, knob):
         c.finish()
         t2 = c.fetch()
         assert_links(c.dbjg_links(), links_ref(t2)[:2], f"{setname} k={k} high load")
+    finally:
+        c.close()
+
+
+def link_lines(t, nxt, status):
+    """The links by key instead of by row (the rows' order may differ from count to count), sorted."""
+    strs = m.keys_to_strings(t.keys, t.k)
+    return sorted((strs[i], d, strs[int(nxt[d, i])] if nxt[d, i] != NO_ROW else "", int(status[d, i]))
+                  for d in (0, 1) for i in range(len(t)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("setname,k", STRIDED)
+def test_strided_launches_give_the_same_links(setname, k, knob):
+    """The test knob query_grid caps the index build and k_dbjg_links at 1 and at 3 workgroups, so their grid-stride loops
+    run many times per thread: the links of the kernels' own grid."""
+    b, o = case_reads(setname, k)
+    c, t = gpu_table(b, o, k)
+    try:
+        assert 2 * len(t) > 3 * 256
+        nxt, status = c.dbjg_links()
+        assert_links((nxt, status), links_ref(t)[:2], f"{setname} k={k}")
+        first = link_lines(t, nxt, status)
+        for grid in (1, 3):
+            c.reset()
+            knob("query_grid", grid)
+            c.add_packed_reads(b, o)
+            c.finish()
+            t2 = c.fetch()
+            n2, s2 = c.dbjg_links()
+            assert_links((n2, s2), links_ref(t2)[:2], f"{setname} k={k} query_grid={grid}")
+            assert link_lines(t2, n2, s2) == first, f"{setname} k={k} query_grid={grid}"
     finally:
         c.close()
 

@@ -15,6 +15,7 @@ import mhm2_proxy_amd as m
 import oracle_lib as O
 from common import edge_case_set, hot_set, synth_set
 from mhm2_proxy_amd import _native as N
+from uutig_lib import palindrome_set
 from query_lib import (NO_ROW, assert_lookup, expected_lookup, mutate_keys, pack_codes, revcomp_keys, row_dict,
                        unpack_codes)
 
@@ -114,6 +115,36 @@ def test_misses(k, n_longs):
     b, o = base_reads()
     with Counted(b, o, k, n_longs=n_longs) as x:
         check_misses(x, b, o, k, n_longs)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [31, 65, 95, 97, 34, 66, 98])
+def test_hits_and_mutants_at_key_word_boundaries(k):
+    """31 bases in one key word, 1 and 31 bases in the third, 1 in the fourth, on a small read set; even k above 32 on a
+    palindromic genome, whose centre k-mer is a multi-word key that is its own reverse complement."""
+    b, o = palindrome_set(k, False, u_len=1200, read_len=160) if k % 2 == 0 else synth_set(600, 3000, 7)
+    with Counted(b, o, k) as x:
+        check_hits(x, k)
+        if k % 2 == 0:
+            assert (revcomp_keys(x.t.keys, k) == x.t.keys).all(axis=1).sum() == 1
+        mut = mutate_keys(x.t.keys, k, np.random.default_rng(k))
+        assert_lookup(x.c.lookup(mut), expected_lookup(x.t, x.d, mut), f"k={k} mutants")
+        assert_lookup(x.c.lookup(mut, True), expected_lookup(x.t, x.d, mut, True), f"k={k} mutants, canonicalize")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("grid", [1, 3])
+@pytest.mark.parametrize("k", [21, 63])
+def test_strided_launches_give_the_same_answers(k, grid, knob):
+    """The test knob query_grid caps the index build and the lookups at 1 and at 3 workgroups, so their grid-stride loops
+    run many times per thread: the answers of the kernels' own grid (which test_hits and test_misses pin to the same
+    expectations)."""
+    b, o = base_reads()
+    knob("query_grid", grid)
+    with Counted(b, o, k) as x:
+        assert len(x.t) > 3 * 256
+        check_hits(x, k)
+        check_misses(x, b, o, k, 0)
 
 
 @pytest.mark.gpu
@@ -298,6 +329,7 @@ def test_null_handle_queries_fail_cleanly():
     assert L.mhmkc_dbjg_links_device(None, None, None) == -1
     assert N.MHMKC_NO_ROW == NO_ROW == 0xFFFFFFFF
     assert L.mhmkc_debug_set(b"query_slots_log2", 0) == 0
+    assert L.mhmkc_debug_set(b"query_grid", 3) == 0 and L.mhmkc_debug_set(b"query_grid", 0) == 0
 
 
 def test_query_helpers_roundtrip():

@@ -7,6 +7,11 @@ against the two walkers that keep a visited array (query_lib.walk_links, and the
 include/mhmkc_dbjg.hpp through tools/bin/libmhmkc_dbjg.so) and assert that the inputs hold every structure of the rule.
 The GPU tests compare the library with it on the GPU's own fetched table, check every row against its contig's bases
 independently of the restatement, and run the multi-k chain with each round's uutigs fed to the next.
+
+NEW_CASES are small tables (one row to a few thousand) built for what random reads do not hold: contigs whose start keys
+agree in their first one, two or three key words (the contig ids then rest on the later passes of the start sort), cycles
+of 2^r - 1, 2^r and 2^r + 1 rows and several cycles beside a path (both branches of both parity steps of the cycle phase),
+one- and two-row tables, and k at the key-word boundaries. The test knob query_grid makes the grid-stride loops stride.
 """
 from __future__ import annotations
 
@@ -23,7 +28,8 @@ import mhm2_proxy_amd as m
 from mhm2_proxy_amd import _native as N
 from common import edge_case_set, hot_set, oracle_table, synth_set
 from query_lib import NO_ROW, links_ref, walk_links
-from uutig_lib import STRUCTURES, circular_set, palindrome_set, ref_lines, revcomp, tie_set, uutigs_ref
+from uutig_lib import (MULTI_CYCLES, MULTI_LINEAR, STRUCTURES, TIE_X, circular_set, common_prefix, cycle_set,
+                       multi_cycle_set, order_tie_set, palindrome_set, ref_lines, revcomp, tie_set, tiny_set, uutigs_ref)
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -31,6 +37,21 @@ CPU_CASES = ([("synth", k) for k in (21, 22, 33, 63)] + [("edge", 21), ("edge", 
              + [(f"pal{w}", k) for k in (6, 22, 32) for w in ("", "+")] + [("pal", 21), ("tie", 35), ("tie", 77)])
 # the library takes no k % 32 == 0 (mhmkc_create), so the k = 32 palindromes stay with the CPU tests
 GPU_CASES = [c for c in CPU_CASES if c[1] % 32] + [("synth", k) for k in (77, 99, 127)]
+
+# Start keys that agree in their first `word` key words. otie<word>: six contigs whose ids are decided in word `word` (one
+# to three words agree; 2, 3 and 4 sort passes); tie<word>: one contig whose two smallest keys first differ in word `word`
+ORDER_TIES = [(f"otie{w}", k) for k, w in ((35, 1), (77, 1), (77, 2), (99, 2), (99, 3), (127, 3), (127, 1))]
+TIES = [(f"tie{w}", k) for k, w in ((77, 2), (99, 3), (127, 3), (127, 2))]
+# one cycle of 2^r - 1, 2^r, 2^r + 1 rows; several cycles of different lengths beside a path and a self-loop
+CYCLE_LENGTHS = tuple(2**r + d for r in range(5, 10) for d in (-1, 0, 1))
+CYCLES = [(f"cyc{n}", 21) for n in CYCLE_LENGTHS] + [("multi", 21)]
+TINY = [(f"tiny{rows}", k) for k in (21, 63) for rows in (1, 2)]
+# key-word boundaries: 31 bases in one word, 1 and 31 bases in the third, 1 in the fourth; even k above 32 (the palindrome's
+# non-mutual port on a multi-word key) and the hairpins next to them
+BOUNDARY = ([(f"pal{w}", k) for k in (34, 66, 98) for w in ("", "+")] + [("pal", k) for k in (33, 65, 97)]
+            + [("circ", k) for k in (31, 65, 95, 97)])
+NEW_CASES = ORDER_TIES + TIES + CYCLES + TINY + BOUNDARY
+CPU_CASES = CPU_CASES + NEW_CASES
 
 
 @functools.lru_cache(maxsize=None)
@@ -41,11 +62,22 @@ def case_reads(setname, k):
         return edge_case_set()
     if setname == "hot":
         return hot_set()
+    long_reads = {"read_len": 160} if k > 90 else {}  # (a read of 100 holds too few windows of such a k for the tiling)
     if setname == "circ":
-        return circular_set()
+        return circular_set(**long_reads)
     if setname == "tie":
         return tie_set()
-    return palindrome_set(k, setname.endswith("+"))
+    if setname.startswith("otie"):
+        return order_tie_set(int(setname[4:]))
+    if setname.startswith("tie"):
+        return tie_set(word=int(setname[3:]), **long_reads)
+    if setname.startswith("cyc"):
+        return cycle_set(int(setname[3:]))
+    if setname == "multi":
+        return multi_cycle_set()
+    if setname.startswith("tiny"):
+        return tiny_set(k, int(setname[4:]))
+    return palindrome_set(k, setname.endswith("+"), **long_reads)
 
 
 @functools.lru_cache(maxsize=None)
@@ -124,6 +156,74 @@ def test_inputs_hold_every_structure():
                 assert ("nonmutual_start" if setname.endswith("+") else "nonmutual_inner") in ref["met"]
                 assert ref["n_nonmutual"] == 1
     assert met == set(STRUCTURES)
+
+
+def test_new_inputs_hold_their_structure():
+    """CPU: what the tie, cycle, tiny and word-boundary inputs are for, asserted on the oracle's tables, so that a change
+    to a generator cannot lose it."""
+    for setname, k in NEW_CASES:
+        t, _, _, ref = cpu_case(setname, k)
+        what = f"{setname} k={k}"
+        strs = sorted(m.keys_to_strings(t.keys, k))
+        if setname.startswith("otie"):  # six paths; the start keys agree in exactly their first `word` words
+            word = int(setname[4:])
+            assert len(ref["seqs"]) == 6 and ref["met"] == {"path"}, what
+            assert all(s.startswith(TIE_X) for s in ref["start_keys"]), what
+            assert ref["start_keys"] == sorted(ref["start_keys"]) == strs[:6], what
+            assert common_prefix(ref["start_keys"]) == 32 * word, what
+        elif setname.startswith("tie"):  # one contig; its two smallest keys agree in exactly their first `word` words
+            word = int(setname[3:])
+            assert len(ref["seqs"]) == 1 and strs[0].startswith(TIE_X) and common_prefix(strs[:2]) == 32 * word, what
+        elif setname.startswith("cyc"):
+            n = int(setname[3:])
+            assert len(t) == n and ref["n_kmers"].tolist() == [n] and ref["cyclic"].tolist() == [True], what
+        elif setname == "multi":
+            sizes = sorted((1,) + MULTI_CYCLES + (MULTI_LINEAR - k - 1,))
+            assert len(t) == sum(sizes) == 1545 and sorted(ref["n_kmers"].tolist()) == sizes, what
+            assert sorted(ref["n_kmers"][ref["cyclic"]].tolist()) == sorted((1,) + MULTI_CYCLES), what
+            assert ref["met"] == {"cycle_one", "cycle_many", "path"}, what
+        elif setname.startswith("tiny"):
+            rows = int(setname[4:])
+            assert len(t) == rows and ref["n_kmers"].tolist() == [rows], what
+        elif setname == "circ":
+            assert ref["n_kmers"].tolist() == [500] and ref["cyclic"].all(), what
+        elif k % 2:
+            assert "hairpin" in ref["met"], what
+        else:  # a key of two, three, four words that is its own reverse complement
+            assert ("nonmutual_start" if setname.endswith("+") else "nonmutual_inner") in ref["met"], what
+            assert ref["n_nonmutual"] == 1 and k > 32, what
+
+
+def cycle_phase_parities(n: int, longest_path: int, longest_cycle: int):
+    """The two parity-dependent steps of the cycle phase of uutigs_build (mhm2_proxy_amd/csrc/mhmkc_host.cpp) for a table
+    of n rows that holds a cycle: (extra & 1 before `extra += extra & 1`, whether the closing `if (F != F0)` round runs).
+      max_rounds: the smallest r >= 1 with 2^r >= 2 n, plus 1 ("int max_rounds = 1; while ((1ull << max_rounds) < 2 * n)
+        max_rounds++; max_rounds++;").
+      rounds of the first loop ("while (rounds < max_rounds)", left at "if (!active || active == prev) break;"): after
+        round r a port is done iff its end is at most 2^r - 1 ports away, so the paths' ports, at most longest_path - 1
+        from their end, are done after max(1, ceil(log2 longest_path)) rounds, and the count stands still one round later;
+        a table of cycles alone stops after 2.
+      extra = max(0, max_rounds - rounds) ("int extra = std::max(0, max_rounds - rounds);").
+      closing rounds ("for (int x = 0; left && x <= max_rounds; x++)"): the opened cycle of L rows is a path of L rows,
+        done after max(1, ceil(log2 L)) rounds; an odd number leaves F != F0."""
+    max_rounds = max(1, (2 * n - 1).bit_length()) + 1
+    rounds = min(max_rounds, max(1, (max(1, longest_path) - 1).bit_length()) + 1)
+    extra = max(0, max_rounds - rounds)
+    closing = max(1, (longest_cycle - 1).bit_length())
+    return extra & 1, closing & 1
+
+
+def test_cycle_inputs_reach_both_branches_of_both_parity_steps():
+    """CPU: over the cycle sweep and `multi`, `extra` is odd and even before it is rounded up, and the number of closing
+    rounds is odd and even (the `if (F != F0)` round runs and does not)."""
+    seen = set()
+    for setname, k in CYCLES:
+        t, _, _, ref = cpu_case(setname, k)
+        paths = ref["n_kmers"][~ref["cyclic"]]
+        seen.add(cycle_phase_parities(len(t), int(paths.max()) if len(paths) else 0, int(ref["n_kmers"][ref["cyclic"]].max())))
+    assert {x[0] for x in seen} == {0, 1} and {x[1] for x in seen} == {0, 1}, seen
+    # the arithmetic by hand: 31 rows: max_rounds 7, extra 5, 5 closing rounds; 33 rows: max_rounds 8, extra 6, 6 closing
+    assert cycle_phase_parities(31, 0, 31) == (1, 1) and cycle_phase_parities(33, 0, 33) == (0, 0)
 
 
 # ---- GPU
@@ -212,6 +312,92 @@ def test_uutigs_equal_the_restated_rule(setname, k, knob):
         c.finish()
         _, (o2, s2, d2, m2), _ = assert_uutigs(c, c.fetch(), f"{setname} k={k} second count")
         assert contig_strings(o2, s2) == first[0] and (d2 == first[1]).all() and (m2 == first[2]).all()
+    finally:
+        c.close()
+
+
+def assert_start_order(c, t, what):
+    """Independent of the restatement: the contigs' smallest keys, read from the row map and the table as strings,
+    increase strictly with the contig id, and for odd k the row that holds a contig's smallest key lies forward in it."""
+    k = t.k
+    strs = m.keys_to_strings(t.keys, k)
+    row_ctg, _, row_rc = c.uutig_rows()
+    n_ctgs = len(c.uutigs()[2])
+    smallest = [None] * n_ctgs
+    for i in np.flatnonzero(row_ctg != NO_ROW):
+        cc = int(row_ctg[i])
+        if smallest[cc] is None or strs[i] < smallest[cc][0]:
+            smallest[cc] = (strs[i], int(i))
+    assert all(x is not None for x in smallest), what
+    keys = [x[0] for x in smallest]
+    assert all(a < b for a, b in zip(keys, keys[1:])), f"{what}: contig ids do not follow the start keys: {keys}"
+    if k % 2:
+        assert all(row_rc[i] == 0 for _, i in smallest), what
+    return keys
+
+
+def assert_cycle_info(c, ref, what):
+    """uutigs_info of the build against the restated rule: the ports on cycles, and what uutigs_build fixes about the
+    cycle phase's rounds (none without a cycle; an even number with one: `extra` is rounded up to even and the closing
+    rounds come in pairs)."""
+    info = c.uutigs_info()
+    on_cycles = int(ref["n_kmers"][ref["cyclic"]].sum())
+    assert info["cycle_ports"] == 2 * on_cycles, what
+    assert (info["cycle_rounds"] > 0) == (on_cycles > 0) and info["cycle_rounds"] % 2 == 0, f"{what}: {info}"
+    if on_cycles:
+        assert info["rounds"] >= 2, what
+    assert (info["n_ctgs"], info["n_bases"]) == (len(ref["seqs"]), int(ref["offsets"][-1])), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("setname,k", NEW_CASES)
+def test_new_cases_equal_the_restated_rule(setname, k):
+    """One small count per case: the start keys that agree in one, two and three key words, the cycle lengths around
+    the powers of two, several cycles beside a path, tables of one and two rows, and the key-word boundaries."""
+    b, o = case_reads(setname, k)
+    c, t = gpu_table(b, o, k)
+    try:
+        what = f"{setname} k={k}"
+        ref = assert_uutigs(c, t, what)[0]
+        assert len(t) == len(cpu_case(setname, k)[0]) and len(ref["seqs"]) == len(cpu_case(setname, k)[3]["seqs"]), what
+        assert_cycle_info(c, ref, what)
+        if "tie" in setname:
+            keys = assert_start_order(c, t, what)
+            word = int(setname[-1])
+            tied = keys if setname.startswith("otie") else sorted(m.keys_to_strings(t.keys, k))[:2]
+            assert len(keys) == (6 if setname.startswith("otie") else 1) and common_prefix(tied) == 32 * word, what
+    finally:
+        c.close()
+
+
+STRIDED = [("synth", 21), ("multi", 21), ("otie3", 99), ("pal+", 22)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("setname,k", STRIDED)
+def test_strided_launches_give_the_same_uutigs(setname, k, knob):
+    """The test knob query_grid caps every query and uutig kernel at 1 and at 3 workgroups (256 and 768 threads, which
+    divide neither the ports nor each other's strides evenly), so every grid-stride loop runs many times per thread and
+    the lanes of k_uutig_jump leave it at different iterations before the wave's sum: the same contigs as the kernels'
+    own grid gives."""
+    b, o = case_reads(setname, k)
+    c, t = gpu_table(b, o, k)
+    try:
+        assert 2 * len(t) > 2 * 256  # one workgroup strides over the ports at least twice
+        _, (offsets, seqs, depths, n_kmers), _ = assert_uutigs(c, t, f"{setname} k={k}")
+        first = (contig_strings(offsets, seqs), depths.copy(), n_kmers.copy())
+        for grid in (1, 3):
+            c.reset()
+            knob("query_grid", grid)
+            c.add_packed_reads(b, o)
+            c.finish()
+            what = f"{setname} k={k} query_grid={grid}"
+            t2 = c.fetch()
+            ref, (o2, s2, d2, m2), _ = assert_uutigs(c, t2, what)
+            assert contig_strings(o2, s2) == first[0] and (d2 == first[1]).all() and (m2 == first[2]).all(), what
+            assert_cycle_info(c, ref, what)
+            if setname.startswith("otie"):
+                assert_start_order(c, t2, what)
     finally:
         c.close()
 

@@ -31,9 +31,10 @@ def random_genome(n: int, seed: int) -> str:
 
 
 def circular_set(n: int = 500, seed: int = 77, read_len: int = 100, step: int = 7):
-    """A circular genome of n bases read with wrap-around, each read three times: at k <= read_len one cycle of n rows."""
+    """A circular genome of n bases read with wrap-around, each read three times: at k <= read_len one cycle of n rows
+    (the genome is repeated until a read fits, so n may be smaller than a read)."""
     g = random_genome(n, seed)
-    gg = g + g
+    gg = g * (2 + read_len // n)
     reads = [gg[a:a + read_len] for a in range(0, n, step)]
     return pack_reads([r for r in reads for _ in range(3)])
 
@@ -50,21 +51,84 @@ def palindrome_set(k: int, with_start: bool, seed: int = 91, u_len: int = 300, r
     return pack_reads([g[a:a + read_len] for a in starts for _ in range(3)])
 
 
-def tie_set(seed: int = 33, r_len: int = 120, read_len: int = 100, step: int = 7):
+TIE_X = "A" * 16 + "C" + "A" * 15  # the first key word of every tied key
+
+
+def tie_shared(word: int, seed: int = 133) -> str:
+    """The 32 (word - 1) bases that follow TIE_X in every tied key: with them the keys share their first `word` words."""
+    return random_genome(32 * (word - 1), seed)
+
+
+def tiled(g: str, read_len: int, step: int) -> list:
+    """Reads of read_len bases every step bases of the linear genome g and one at its end, each three times."""
+    starts = list(range(0, len(g) - read_len, step)) + [len(g) - read_len]
+    return [g[a:a + read_len] for a in starts for _ in range(3)]
+
+
+def tie_set(seed: int = 33, r_len: int = 120, read_len: int = 100, step: int = 7, word: int = 1):
     """A genome in which X = A^16 C A^15 occurs twice, followed by C and by T: for 35 <= k <= 100 the two k-mers that
     begin with X are the smallest keys of their (single) component and share their first key word, so the start is
-    decided by the later words."""
-    x = "A" * 16 + "C" + "A" * 15
+    decided by the later words. word > 1 puts the same 32 (word - 1) bases between X and the C / T: the two keys share
+    exactly their first `word` words (k >= 32 word + 3)."""
+    x = TIE_X + tie_shared(word)
     r = [random_genome(r_len, seed + i) for i in range(3)]
     g = r[0] + "G" + x + "C" + r[1] + "G" + x + "T" + r[2]
-    starts = list(range(0, len(g) - read_len, step)) + [len(g) - read_len]
-    return pack_reads([g[a:a + read_len] for a in starts for _ in range(3)])
+    return pack_reads(tiled(g, read_len, step))
+
+
+def order_tie_set(word: int, n_gen: int = 6, seed: int = 214, r_len: int = 150, read_len: int = 160, step: int = 7):
+    """n_gen separate linear genomes R_j + PRE_j + X + S + R'_j (X, S as in tie_set; PRE_j two bases over C, G, T, distinct
+    per genome, so that no two genomes share a k-mer and none holds a smaller key): n_gen paths whose start keys all
+    begin with X + S, so their order, the contigs' ids, is decided in key word `word` (counted from 0) at the earliest."""
+    x = TIE_X + tie_shared(word)
+    pres = [a + b for a in "CGT" for b in "CGT"][:n_gen]
+    assert len(pres) == n_gen
+    reads = []
+    for j, pre in enumerate(pres):
+        g = random_genome(r_len, seed + 2 * j) + pre + x + random_genome(r_len, seed + 2 * j + 1)
+        reads += tiled(g, read_len, step)
+    return pack_reads(reads)
+
+
+def cycle_set(length: int, seed: int = 401):
+    """A circular genome of `length` bases: at k = 21 one cycle of exactly `length` rows."""
+    return circular_set(length, seed + length)
+
+
+MULTI_CYCLES = (33, 64, 257, 512)
+MULTI_LINEAR = 700
+
+
+def multi_cycle_set(seed: int = 501, read_len: int = 100, step: int = 7):
+    """Circular genomes of MULTI_CYCLES bases, a linear one of MULTI_LINEAR bases and three poly-A reads: at k = 21
+    cycles of 1, 33, 64, 257 and 512 rows beside a path of MULTI_LINEAR - k - 1 rows."""
+    reads = []
+    for j, n in enumerate(MULTI_CYCLES):
+        g = random_genome(n, seed + j)
+        gg = g * (2 + read_len // n)
+        reads += [gg[a:a + read_len] for a in range(0, n, step) for _ in range(3)]
+    reads += tiled(random_genome(MULTI_LINEAR, seed + len(MULTI_CYCLES)), read_len, step)
+    reads += ["A" * read_len] * 3
+    return pack_reads(reads)
+
+
+def tiny_set(k: int, rows: int, seed: int = 601):
+    """One random read of k + 1 + rows bases, three times: `rows` rows with both extensions, one contig."""
+    return pack_reads([random_genome(k + 1 + rows, seed + k)] * 3)
+
+
+def common_prefix(strs) -> int:
+    """The number of leading bases that all the strings share."""
+    n = 0
+    while all(len(s) > n and s[n] == strs[0][n] for s in strs):
+        n += 1
+    return n
 
 
 def uutigs_ref(t: m.KmerTable, nxt: np.ndarray, status: np.ndarray) -> dict:
     """mhmkc_uutigs restated (include/mhmkc.h): ports, mutual links, components, start, layout, depth, order, strand and
     the row map, from the table and its links alone. Returns offsets, seqs (list of str), depths, n_kmers, row_ctg,
-    row_pos, row_rc, the set of STRUCTURES met and the numbers of walkable rows and of non-mutual ports."""
+    row_pos, row_rc, cyclic (per contig: a cycle), start_keys (per contig), the set of STRUCTURES met and the numbers of walkable rows and of non-mutual ports."""
     n, k = len(t), t.k
     strs = m.keys_to_strings(t.keys, k) if n else []
     counts = [int(x) for x in t.counts]
@@ -127,7 +191,7 @@ def uutigs_ref(t: m.KmerTable, nxt: np.ndarray, status: np.ndarray) -> dict:
                 comp_of[r] = len(comps)
             comps.append((chain, True))
 
-    recs = []
+    recs = []  # (start key, bases, depth, placed rows, is a cycle)
     for chain, cyc in comps:
         mrows = len(chain)
         s = min((r for r, _ in chain), key=lambda r: strs[r])
@@ -149,20 +213,21 @@ def uutigs_ref(t: m.KmerTable, nxt: np.ndarray, status: np.ndarray) -> dict:
         for r, _ in chain:
             if r in nonmutual:
                 met.add("nonmutual_start" if r == s else "nonmutual_inner")
-        recs.append((strs[s], seq, depth, placed))
+        recs.append((strs[s], seq, depth, placed, cyc))
     recs.sort(key=lambda x: x[0])
 
     row_ctg = np.full(n, NO_ROW, dtype=np.uint32)
     row_pos = np.zeros(n, dtype=np.uint32)
     row_rc = np.zeros(n, dtype=np.uint8)
     offsets = np.zeros(len(recs) + 1, dtype=np.uint64)
-    for c, (_, seq, _, placed) in enumerate(recs):
+    for c, (_, seq, _, placed, _) in enumerate(recs):
         offsets[c + 1] = int(offsets[c]) + len(seq)
         for pos, r, rc in placed:
             row_ctg[r], row_pos[r], row_rc[r] = c, pos, rc
     return {"offsets": offsets, "seqs": [x[1] for x in recs], "depths": np.array([x[2] for x in recs], dtype=np.float64),
             "n_kmers": np.array([len(x[3]) for x in recs], dtype=np.uint32), "row_ctg": row_ctg, "row_pos": row_pos,
-            "row_rc": row_rc, "met": met, "n_walkable": sum(walkable), "n_nonmutual": n_nonmutual}
+            "row_rc": row_rc, "cyclic": np.array([x[4] for x in recs], dtype=bool), "start_keys": [x[0] for x in recs],
+            "met": met, "n_walkable": sum(walkable), "n_nonmutual": n_nonmutual}
 
 
 def ref_lines(ref: dict) -> list:
