@@ -40,7 +40,11 @@ extern "C" {
  *                 probe chains and the wrap past the last slot
  *   query_grid    at most v workgroups for every kernel of the queries and the uutigs (kcount_query.hip,
  *                 kcount_uutig.hip; the library sorts and scans keep their own grids), so that their grid-stride loops
- *                 run more than once per thread on a small table (0: the kernels' own grids) */
+ *                 run more than once per thread on a small table (0: the kernels' own grids)
+ *   merge_grid    at most v workgroups (four waves each, one read pair per wave and turn) for k_fq_merge, both
+ *                 instances, and k_fq_merge_pack (fastq.hip), so that a wave merges and packs several pairs in turn on a
+ *                 small batch: the prefetched next descriptor, the reuse of the wave's LDS after another pair (0: the
+ *                 launches' own grids) */
 int mhmkc_debug_set(const char *knob, int64_t value);
 /* Every knob back to its default. */
 void mhmkc_debug_reset(void);

@@ -1108,12 +1108,13 @@ hipError_t launch_fq_merge(const char *text, uint64_t n, const unsigned long lon
   uint32_t *long_list = long_pairs(desc_buf, n_pairs);
   hipError_t e = hipSuccess;
   // grid-stride over the pairs, one wave each; enough waves to fill the chip several times over
+  // (merge_grid_for: the test knob merge_grid caps the workgroups; the product's launches are these)
   const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_pairs + MG_WAVES - 1) / MG_WAVES, 16384));
-  k_fq_merge<MG_SHORT><<<dim3((unsigned)blocks), dim3(64 * MG_WAVES), 0, s>>>(
+  k_fq_merge<MG_SHORT><<<dim3((unsigned)merge_grid_for(blocks)), dim3(64 * MG_WAVES), 0, s>>>(
       text, desc, n_pairs, rec_offs, qual_offset, scratch, pair_info, out_len, err, stats, nullptr);
   if ((e = hipGetLastError()) != hipSuccess || MG_SHORT >= MG_MAXL) return e;
   // the listed long pairs (the waves of an empty list exit at once)
-  k_fq_merge<MG_MAXL><<<dim3((unsigned)std::min<uint64_t>(blocks, 1024)), dim3(64 * MG_WAVES), 0, s>>>(
+  k_fq_merge<MG_MAXL><<<dim3((unsigned)merge_grid_for(std::min<uint64_t>(blocks, 1024))), dim3(64 * MG_WAVES), 0, s>>>(
       text, desc, n_pairs, rec_offs, qual_offset, scratch, pair_info, out_len, err, stats, long_list);
   return hipGetLastError();
 }
@@ -1124,7 +1125,7 @@ hipError_t launch_fq_merge_pack(const char *text, const void *desc_buf, uint64_t
                                 unsigned long long *err, hipStream_t s) {
   if (!n_pairs) return hipSuccess;
   const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_pairs + MG_WAVES - 1) / MG_WAVES, 16384));
-  k_fq_merge_pack<<<dim3((unsigned)blocks), dim3(64 * MG_WAVES), 0, s>>>(
+  k_fq_merge_pack<<<dim3((unsigned)merge_grid_for(blocks)), dim3(64 * MG_WAVES), 0, s>>>(
       text, (const PairDesc *)desc_buf, n_pairs, rec_offs, scratch, pair_info, out_offs, qual_offset, out, err);
   return hipGetLastError();
 }

@@ -427,6 +427,12 @@ inline unsigned query_grid_for(uint64_t n) {
   const uint64_t g = n + 255 < 16384ull * 256 ? (n + 255) / 256 : 16384;
   return (unsigned)(g < 1 ? 1 : (query_grid_cap && query_grid_cap < g ? query_grid_cap : g));
 }
+// Workgroups of the read-pair merge's grid-stride launches (fastq.hip: launch_fq_merge, both instances, and
+// launch_fq_merge_pack), four waves each, one pair per wave and turn. The test knob merge_grid (include/mhmkc_debug.h)
+// caps them at merge_grid_cap, so that a wave takes several pairs in turn on a small batch; 0, the product's value: the
+// launches' own grids.
+inline unsigned merge_grid_cap = 0;
+inline uint64_t merge_grid_for(uint64_t blocks) { return merge_grid_cap && merge_grid_cap < blocks ? merge_grid_cap : blocks; }
 // nl = k/32 + 1 key words (1..4) of the nlo words per row / query
 hipError_t launch_query_build(const uint64_t *keys, uint64_t n, int nl, int nlo, const QueryIndex &ix, hipStream_t s);
 // rows[i] = the row of query i (0xFFFFFFFF: not in the table), counts / left / right its fields (0 on a miss); any

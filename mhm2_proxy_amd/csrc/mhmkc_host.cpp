@@ -69,6 +69,8 @@ struct DebugKnobs {
   int64_t query_slots_log2 = 0;   // slots of the query index, as a power of two (0: the smallest one >= 2 n_out)
   // query_grid, the most workgroups of every query / uutig kernel (0: the kernels' own grids), lives where the launches
   // of kcount_query.hip and kcount_uutig.hip read it: mhm::query_grid_cap (kcount_launch.hpp)
+  // merge_grid, the most workgroups of the read-pair merge's launches (0: their own grids), likewise lives where
+  // fastq.hip's launches read it: mhm::merge_grid_cap (kcount_launch.hpp)
 };
 DebugKnobs g_dbg;
 
@@ -4413,6 +4415,7 @@ int mhmkc_debug_set(const char *knob, int64_t value) {
   else if (k == "cb0_3") g_dbg.cb0[3] = value;
   else if (k == "query_slots_log2") g_dbg.query_slots_log2 = value;
   else if (k == "query_grid") mhm::query_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
+  else if (k == "merge_grid") mhm::merge_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else return MHMKC_EINVAL;
   return MHMKC_OK;
 }
@@ -4420,6 +4423,7 @@ int mhmkc_debug_set(const char *knob, int64_t value) {
 void mhmkc_debug_reset(void) {
   g_dbg = DebugKnobs();
   mhm::query_grid_cap = 0;
+  mhm::merge_grid_cap = 0;
 }
 
 int mhmkc_debug_nib_pack(const uint8_t *src, uint64_t n, uint8_t *dst, int qcut, int mode) {

@@ -53,8 +53,16 @@ def fast_count_mismatches(a: str, b: str, n: int, mx: int) -> int:
     return mm
 
 
-def merge_pair(seq1, quals1, seq2, quals2, off):
-    """-> (reads [(seq, quals)], merged, ambiguous_increments, overlap)"""
+def merge_pair(seq1, quals1, seq2, quals2, off, trace=None):
+    """-> (reads [(seq, quals)], merged, ambiguous_increments, overlap)
+
+    trace, if given, is a dict that is filled in (the results are the same with and without it): "len", "start_i",
+    "scans": one dict per offset that passed the fast filter, in order, with "i" the offset, "overlap", "break" (None,
+    or "bothN2" :364-368, "manyN" :408-412, "mismatch" :413, "quality" :392-396) and "break_j" its position in the
+    overlap, "matches", "mismatches", "perror" as the loop left them, and "verdict" ("good" :417-418, "weak" :431, or
+    None; None too for a scan that the quality error ended); "exit": which of the three ambiguity exits ended the
+    offset loop ("abort" :347 after an N rule, "good_again" :424-429, "weak_after_good" :434-440), or None; and
+    "best_i" / "found_i" as they stood at the end."""
     quals1 = list(quals1)
     rc = "".join(COMP[c] for c in reversed(seq2))
     rq = list(reversed(quals2))
@@ -65,6 +73,9 @@ def merge_pair(seq1, quals1, seq2, quals2, off):
     ln = min(len(rc), len(seq1))
     start_i = 0 if ln == len(seq1) else len(seq1) - ln
     found_i = best_i = -1
+    scans = []
+    if trace is not None:
+        trace.update({"len": ln, "start_i": start_i, "scans": scans, "exit": None, "best_i": -1, "found_i": -1})
     for i in range(ln - MIN_OVERLAP + EXTRA):
         if abort:
             break
@@ -75,6 +86,8 @@ def merge_pair(seq1, quals1, seq2, quals2, off):
             continue
         matches = mism = both = ncount = checked = 0
         perror = 0.0
+        sc = {"i": i, "overlap": ov, "break": None, "break_j": None, "verdict": None}
+        scans.append(sc)
         for j in range(ov):
             checked += 1
             p = start_i + i + j
@@ -87,6 +100,7 @@ def merge_pair(seq1, quals1, seq2, quals2, off):
                     if both > 1:
                         abort += 1
                         amb += 1
+                        sc.update({"break": "bothN2", "break_j": j})
                         break
             else:
                 mism += 1
@@ -100,6 +114,8 @@ def merge_pair(seq1, quals1, seq2, quals2, off):
                     rq[j] = chr(off)
                 q1, q2 = (ord(quals1[p]) - off) & 0xFF, (ord(rq[j]) - off) & 0xFF
                 if q1 >= len(Q2PERROR) or q2 >= len(Q2PERROR):
+                    sc.update({"break": "quality", "break_j": j, "matches": matches, "mismatches": mism,
+                               "perror": perror})
                     raise ValueError("qual")
                 if ps == "N":
                     perror += Q2PERROR[q2]
@@ -110,23 +126,36 @@ def merge_pair(seq1, quals1, seq2, quals2, off):
             if ncount > 3:
                 abort += 1
                 amb += 1
+                sc.update({"break": "manyN", "break_j": j})
                 break
             if mism > emax:
+                sc.update({"break": "mismatch", "break_j": j})
                 break
+        sc.update({"matches": matches, "mismatches": mism, "perror": perror})
         thr = max(ov - tmax, MIN_OVERLAP)
         if matches >= thr and checked == ov and mism <= tmax and perror / ov <= MAX_PERROR:
+            sc["verdict"] = "good"
             if best_i < 0 and found_i < 0:
                 best_i = i
             else:
                 amb += 1
                 best_i = -1
+                if trace is not None:
+                    trace["exit"] = "good_again"
                 break
         elif checked == ov and mism <= emax and perror / ov <= MAX_PERROR * 4 / 3:
+            sc["verdict"] = "weak"
             found_i = i
             if best_i >= 0:
                 amb += 1
                 best_i = -1
+                if trace is not None:
+                    trace["exit"] = "weak_after_good"
                 break
+    if trace is not None:
+        if abort and trace["exit"] is None:
+            trace["exit"] = "abort"
+        trace.update({"best_i": best_i, "found_i": found_i})
     if best_i >= 0 and not abort:
         ov = ln - best_i
         maxq = 41 + off
