@@ -1785,6 +1785,23 @@ __device__ __forceinline__ uint32_t lds_add_late(unsigned int *p, uint32_t v) {
   return __hip_atomic_fetch_add(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// Guided tail of k_count's dynamic cold sweeps (see the round loop): the last MHMKC_TAIL_SLOTS wave slots of a sweep go
+// out as MHMKC_TAIL_DIV sub-slots each (1: whole slots to the end); ...2: two-word keys. Off (A/B variants only): a
+// sub-slot issues a whole slot's instructions for a part of its records, which cost more than the shorter wait at the
+// sweep's barrier gave back at every size tried (round 7, DESIGN.md §4.2: C2 k_count 4.68-4.85 -> 4.67-4.94 ms with the
+// last 4 slots in halves, 4.98-5.13 in quarters, 6.05-6.32 with the last 16 in quarters).
+#ifndef MHMKC_TAIL_DIV
+#define MHMKC_TAIL_DIV 1
+#endif
+#ifndef MHMKC_TAIL_SLOTS
+#define MHMKC_TAIL_SLOTS 4
+#endif
+#ifndef MHMKC_TAIL_DIV2
+#define MHMKC_TAIL_DIV2 1
+#endif
+#ifndef MHMKC_TAIL_SLOTS2
+#define MHMKC_TAIL_SLOTS2 4
+#endif
 // Groups a key may probe before its record is deferred to the next sweep of its bucket.
 constexpr int C_PROBE = 64;
 // First-group reads a lane keeps in flight in phase A (two-word keys: one at a time, measured 11.39 -> 11.24 ms at
@@ -1964,13 +1981,27 @@ __device__ __forceinline__ uint32_t lds_add(const CountLds<K> &t, int slot, uint
 // the wave. slot_count() reads it back; ctg_apply stores an explicit count as 0x80000000 | count.
 // (Three adds, count and both extensions: 8.24 -> 8.32 ms in round 1; branch-free adds of 0 by every lane
 // that has nothing to count: 4.85 -> 5.04 ms in round 3.)
+// MHMKC_ADDLUT (round 7): the left add's word from a nibble table of plane numbers counted from the count word (cnt
+// and the four extension planes are contiguous: 0 the count word for left-none, 1 for A/C, 2 for G/T), one
+// shift-and-mask and one 24-bit multiply-add instead of a compare, a multiply and two selects; the addend is a shift
+// of 1; a right-none is skipped (the compiler branched around the right add's address anyway).
+#ifndef MHMKC_ADDLUT
+#define MHMKC_ADDLUT 1
+#endif
 template <typename K>
 __device__ __forceinline__ void lds_add_nr(const CountLds<K> &t, int slot, uint32_t e, uint32_t *dummy) {
+#if MHMKC_ADDLUT
+  const uint32_t pl = (0x2211u >> ((e >> 1) & 0x1cu)) & 3u, r = e & 7u;
+  atomicAdd(&t.cnt[pl * (uint32_t)t.cap + (uint32_t)slot], 1u << ((e & 8u) << 1));
+  if (r < 4u) atomicAdd(&t.cnt[(3u + (r >> 1)) * (uint32_t)t.cap + (uint32_t)slot], 1u << ((e & 1u) << 4));
+  (void)dummy;
+#else
   const uint32_t l = (e >> 3) & 7u, r = e & 7u;
   uint32_t *lw = l < 4u ? &t.ext[(l >> 1) * t.cap + slot] : &t.cnt[slot];
   atomicAdd(lw, (l & 1u) ? 0x10000u : 1u);
   uint32_t *rw = r < 4u ? &t.ext[(2 + (r >> 1)) * t.cap + slot] : dummy;
   atomicAdd(rw, (r & 1u) ? 0x10000u : 1u);
+#endif
 }
 
 // The count of an occupied slot (see lds_add_nr for the cold-sweep encoding).
@@ -2435,22 +2466,47 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
       // DYN: this wave's slot (round cc / NWV, wave slot cc % NWV) and its next one; wave s starts with slots s and
       // NWV + s, every later one comes from s_next (asked for one slot ahead, so the answer is never waited for)
       uint32_t cc = (uint32_t)wid, cn = (uint32_t)wid + NWV;
-      auto slot_first = [&](uint32_t c) { return c / NWV * RND + c % NWV * (RK::C32 ? 256u : 64u); };
+      // A wave slot is SLOT records: consecutive ones (CONTIG: a compact quad per lane, or one record per lane; slot c
+      // starts at record c * SLOT, RND = NWV * SLOT), else R strips of 64, C_THREADS apart, of round c / NWV. Guided
+      // tail (CONTIG only): the sweep's last TAIL_SLOTS wave slots go out as sub-slots of SUB = SLOT / TAIL_DIV
+      // records (compact keys: the quads of lanes 0 .. SUB / 4 - 1; otherwise lanes 0 .. SUB - 1), so that the waves
+      // reach the sweep's barrier within a sub-slot of each other. Slot c -> (first record, size) depends on c and n
+      // alone, so every wave computes it alike: slots below t0 are whole, slot t0 + u is the u-th sub-slot after
+      // them, and the slots end at the first one that starts at or past n. Each wave's first two slots (c < 2 NWV)
+      // are pre-assigned and whole.
+      constexpr uint32_t SLOT = 64u * (uint32_t)R;
+      static_assert(RND == NWV * SLOT, "a round is one wave slot per wave");
+      constexpr bool CONTIG = RK::C32 || R == 1;
+      constexpr uint32_t TAIL_DIV = !CONTIG ? 1 : NL == 1 ? MHMKC_TAIL_DIV : MHMKC_TAIL_DIV2;
+      constexpr uint32_t TAIL_SLOTS = NL == 1 ? MHMKC_TAIL_SLOTS : MHMKC_TAIL_SLOTS2;
+      constexpr uint32_t SUB = SLOT / TAIL_DIV;
+      static_assert(TAIL_DIV >= 1 && SUB * TAIL_DIV == SLOT && SUB % (uint32_t)R == 0, "sub-slots are whole lanes' records");
+      const uint32_t n_slots = (n + SLOT - 1) / SLOT;
+      const uint32_t t0 = n_slots > 2 * NWV + TAIL_SLOTS ? n_slots - TAIL_SLOTS : 2 * NWV;
+      // (not CONTIG: the slot's first strip)
+      auto slot_first = [&](uint32_t c) -> uint32_t {
+        if constexpr (!CONTIG) return c / NWV * RND + c % NWV * 64u;
+        if constexpr (TAIL_DIV == 1) return c * SLOT;
+        return c < t0 ? c * SLOT : t0 * SLOT + (c - t0) * SUB;
+      };
+      auto slot_size = [&](uint32_t c) -> uint32_t { return TAIL_DIV == 1 || c < t0 ? SLOT : SUB; };
       for (uint32_t r0 = 0; DYN ? slot_first(cc) < n : r0 < lim; r0 += RND, rnd++) {
         STAMP(t_r0);
         uint64_t ck[R][NL];
         uint32_t ce[R];
         uint32_t ca = 0;  // DYN: the slot after cn (lane 0 asks now, the answer is read at the end of the round)
         if (DYN && lane == 0) ca = lds_add_late(&s_next, 1u);
-        const uint32_t cr0 = DYN ? cc / NWV * RND : r0;                              // the slot's round
-        const uint32_t vt = DYN ? cc % NWV * 64u + (uint32_t)lane : (uint32_t)tid;  // its thread slot
         // record j of this lane is valid iff j * vstep < vrem: the records left from this lane's first one (a dense
-        // sweep: [r0, n) in thread order; a re-sweep: this wave's own nw positions), saturated at 0
-        const uint32_t vfirst = nw == NONE ? cr0 + (RK::C32 ? 4u * vt : vt)
-                                           : (uint32_t)rnd * (uint32_t)(64 * R) + (RK::C32 ? 4u * (uint32_t)lane : (uint32_t)lane);
-        const uint32_t vend = nw == NONE ? n : nw;
+        // sweep: [r0, n) in thread order; a re-sweep: this wave's own nw positions; a dynamic sweep, always dense:
+        // the slot's records, a lane past a sub-slot has none), saturated at 0
+        const uint32_t cfirst = DYN ? slot_first(cc) : 0u;
+        const uint32_t vfirst = DYN          ? cfirst + (RK::C32 ? 4u * (uint32_t)lane : (uint32_t)lane)
+                                : nw == NONE ? r0 + (RK::C32 ? 4u * (uint32_t)tid : (uint32_t)tid)
+                                             : (uint32_t)rnd * (uint32_t)(64 * R) + (RK::C32 ? 4u * (uint32_t)lane : (uint32_t)lane);
+        const uint32_t cend = DYN && CONTIG ? cfirst + slot_size(cc) : n;
+        const uint32_t vend = DYN ? (cend < n ? cend : n) : nw == NONE ? n : nw;
         const uint32_t vrem = (vend > vfirst ? vend : vfirst) - vfirst;
-        const uint32_t vstep = RK::C32 ? 1u : nw == NONE ? (uint32_t)C_THREADS : 64u;
+        const uint32_t vstep = RK::C32 ? 1u : (DYN || nw == NONE) ? (uint32_t)C_THREADS : 64u;
 #pragma unroll
         for (int j = 0; j < R; j++) {
           const bool valid = (uint32_t)j * vstep < vrem;
@@ -2472,8 +2528,9 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
         // (unconditional: in the last round it re-reads this round's records, never used. A load under a branch
         // left its registers to a phi whose copies made hipcc wait for the load right there, vmcnt(0), so the next
         // round's records were fetched with the whole HBM latency exposed every round)
-        if (DYN)  // (unconditional too: past the records it re-reads the last quad / record)
-          prefetch(ps, n, cn / NWV * RND, NONE, cn % NWV * 64u + (uint32_t)lane);
+        if (DYN)  // (unconditional too: past the records it re-reads the last quad / record; a lane past a sub-slot
+                  // reads the records behind it, inside the bucket's region, and does not use them)
+          prefetch(ps, n, CONTIG ? slot_first(cn) : cn / NWV * RND, NONE, (CONTIG ? 0u : cn % NWV * 64u) + (uint32_t)lane);
         else
           prefetch(ps, n, r0 + RND < lim ? r0 + RND : r0, nw, (uint32_t)tid);
         // A. home-group lookups: the first groups of all R records are read in batches of C_BATCH (the
@@ -2768,17 +2825,25 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
       }
     }
     __syncthreads();
-    const uint32_t n_list = s_fin[0];
+    // (MHMKC_FINX: as a scalar, and a wave leaves pass 2 and the output loop at the first j whose list positions, this
+    // wave's 64 from wid * 64 + j * C_THREADS on, are all past the list: at C2 a bucket lists ~900 slots, fewer than
+    // C_THREADS, so five of the SPT = 6 iterations have no work in any wave)
+#ifndef MHMKC_FINX
+#define MHMKC_FINX 1
+#endif
+    const uint32_t n_list = MHMKC_FINX ? (uint32_t)__builtin_amdgcn_readfirstlane(s_fin[0]) : s_fin[0];
+    const uint32_t fin_w0 = (uint32_t)wid * 64u;
     // per listed slot of this thread: sp = slot | output position << 16 (both < 2^16), row = count | L << 16 | R << 24
     uint32_t surv_mask = 0, sp[SPT], row[SPT];
+#pragma unroll
+    for (int j = 0; j < SPT; j++) sp[j] = 0, row[j] = 0;
     // (uniform) the survivors' key words go to registers: the table may be cleared before the output is written
     const bool kfast = KREG && n_list <= (uint32_t)(KJ * C_THREADS);
     K kreg[KJ][NL];
 #pragma unroll
     for (int j = 0; j < SPT; j++) {
+      if (MHMKC_FINX && fin_w0 + (uint32_t)j * C_THREADS >= n_list) break;
       const uint32_t i = (uint32_t)tid + (uint32_t)j * C_THREADS;
-      sp[j] = 0;
-      row[j] = 0;
       bool sv = false;
       if (i < n_list) {
         const int slot = flist[i];
@@ -2840,6 +2905,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
     if (s_gbase == ~0ull) surv_mask = 0;
 #pragma unroll
     for (int j = 0; j < SPT; j++) {
+      if (MHMKC_FINX && fin_w0 + (uint32_t)j * C_THREADS >= n_list) break;
       if ((surv_mask >> j) & 1u) {
         const int slot = (int)(sp[j] & 0xffffu);
         // the key words: from registers (kfast: every listed slot is one of a thread's first KJ) or from the table
