@@ -1773,6 +1773,7 @@ struct CountLds {
   uint32_t *cnt;   // [cap]
   uint32_t *ext;   // [4][cap]: (A|C<<16, G|T<<16) left, then right
   int cap;         // multiple of 4: slots are probed in groups of 4
+  uint32_t *clog;  // the sweep's clamp log (ext_clamp), or null when no threshold can pass the clamp's target
 };
 
 // An LDS fetch-add whose result is used later (k_count's dynamic slot counter, read at the end of the round): the
@@ -2015,22 +2016,69 @@ __device__ __forceinline__ uint32_t slot_count(const CountLds<K> &t, int slot, b
 }
 
 // Saturation at the decision level: a 16-bit half that reached 0xC000 is CAS-clamped back to 0x8000.
-// Exact for the reference's get_ext, which only compares counters against thresholds
-// <= max((int)(0.1 * 65535), dmin_thres) <= 32768, and whose top base is unique whenever it is chosen
-// (DESIGN.md §3.4); the reference saturates the same counters at 65535 (kcount_cpu.cpp:148-164).
+// Exact as it stands while no threshold of get_ext passes 0x8000: the reference saturates the same counters at 65535
+// (kcount_cpu.cpp:148-164) and compares them with max((int)((1 - DYN_MIN_DEPTH) * count), dmin_thres), and its top
+// base is unique whenever it is chosen. dmin_thres <= 32768 is enforced; the dynamic part stays
+// below 0x8000 only for dyn_min_depth >= 0.5 (the reference's 0.9 gives 6553), which is a property of that setting, not
+// of the reference. With a smaller dyn_min_depth (CountParams.wide_thr) every clamp is logged and the decision reads
+// the counters with the logged amounts put back (clog_add / clog_restore), exact up to the reference's 65535.
 // When to check: a half never exceeds its k-mer's count, and between a lane's count add and its own
 // extension add fewer than S = records per round other adds happen (the round barrier closes the
 // round). So a lane whose count add returned old < 0xC000 - 2S cannot push a half to 0xC000, and every
 // add that does is followed by its own lane's clamp before another S adds: a half stays below
 // 0xC000 + S < 0x10000 and never carries into its neighbour.
-__device__ __forceinline__ void ext_clamp(uint32_t *p, int half) {
+constexpr uint32_t EXT_CLAMP_AT = 0xC000u, EXT_CLAMP_TO = 0x8000u;
+
+// The clamp log of a sweep: words 0 .. CLOG_N - 1 are entries id << 16 | amount, id = slot << 3 | half (halves 0-3 the
+// left counters A C G T, 4-7 the right ones; 0xFFFF: no entry), amount = what the clamps took from that half, no longer
+// added to once it is 0x8000 or more (the half, at least 0x8000 itself, then stands for 65535); word CLOG_N counts the
+// entries asked for. Two clamps of one half lie at least 0x4000 adds to it apart, more than the adds between two round
+// barriers (HOT > 0x8000), so a half's entry is found by its later clamps and never appended twice. An entry costs
+// at least 0xC000 records of the sweep; a sweep that asks for more than CLOG_N of them flags the launch (err bit 5).
+constexpr uint32_t CLOG_N = CLAMP_LOG - 1;
+__device__ __forceinline__ void clog_add(uint32_t *clog, uint32_t id, uint32_t amount) {
+  uint32_t n = __hip_atomic_load(&clog[CLOG_N], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  n = n < CLOG_N ? n : CLOG_N;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t w = __hip_atomic_load(&clog[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if ((w >> 16) == id) {
+      if ((w & 0xffffu) < 0x8000u) atomicAdd(&clog[i], amount);  // (amount < 0x4000 + S: no carry into the id)
+      return;
+    }
+  }
+  const uint32_t i = atomicAdd(&clog[CLOG_N], 1u);
+  if (i < CLOG_N) __hip_atomic_store(&clog[i], id << 16 | amount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// The four extension words of `slot` with the logged amounts put back, each half saturating at 65535 (n entries).
+__device__ __forceinline__ void clog_restore(const uint32_t *clog, uint32_t n, uint32_t slot, uint32_t &e0, uint32_t &e1,
+                                             uint32_t &e2, uint32_t &e3) {
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t w = clog[i];
+    if ((w >> 19) != slot) continue;
+    const uint32_t pl = (w >> 17) & 3u, sh = ((w >> 16) & 1u) * 16u;
+    uint32_t x = pl == 0 ? e0 : pl == 1 ? e1 : pl == 2 ? e2 : e3;
+    uint32_t v = ((x >> sh) & 0xffffu) + (w & 0xffffu);
+    v = v > 65535u ? 65535u : v;
+    x = (x & ~(0xffffu << sh)) | (v << sh);
+    e0 = pl == 0 ? x : e0;
+    e1 = pl == 1 ? x : e1;
+    e2 = pl == 2 ? x : e2;
+    e3 = pl == 3 ? x : e3;
+  }
+}
+
+__device__ __forceinline__ void ext_clamp(uint32_t *p, int half, uint32_t *clog, uint32_t id) {
   uint32_t cur = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   for (int iter = 0; iter < 4096; iter++) {
     const uint32_t f = half ? (cur >> 16) : (cur & 0xffffu);
-    if (f < 0xC000u) break;
-    const uint32_t nw = half ? ((cur & 0xffffu) | 0x80000000u) : ((cur & 0xffff0000u) | 0x8000u);
+    if (f < EXT_CLAMP_AT) break;
+    const uint32_t nw = half ? ((cur & 0xffffu) | EXT_CLAMP_TO << 16) : ((cur & 0xffff0000u) | EXT_CLAMP_TO);
     const uint32_t prev = atomicCAS(p, cur, nw);
-    if (prev == cur) break;
+    if (prev == cur) {
+      if (clog) clog_add(clog, id, f - EXT_CLAMP_TO);
+      break;
+    }
     cur = prev;
   }
 }
@@ -2038,8 +2086,8 @@ __device__ __forceinline__ void ext_clamp(uint32_t *p, int half) {
 template <typename K>
 __device__ __forceinline__ void lds_clamp(const CountLds<K> &t, int slot, uint32_t e) {
   const int l = (int)((e >> 3) & 7u), r = (int)(e & 7u);
-  if (l < 4) ext_clamp(&t.ext[(l >> 1) * t.cap + slot], l & 1);
-  if (r < 4) ext_clamp(&t.ext[(2 + (r >> 1)) * t.cap + slot], r & 1);
+  if (l < 4) ext_clamp(&t.ext[(l >> 1) * t.cap + slot], l & 1, t.clog, (uint32_t)slot << 3 | (uint32_t)l);
+  if (r < 4) ext_clamp(&t.ext[(2 + (r >> 1)) * t.cap + slot], r & 1, t.clog, (uint32_t)slot << 3 | 4u | (uint32_t)r);
 }
 
 // Diagnostic phase stamps of k_count (MHMKC_STAMP builds only): wave cycles per phase, summed into
@@ -2076,7 +2124,7 @@ __device__ __forceinline__ bool slot_survives(uint32_t c32, uint32_t e0, uint32_
 // src/kcount/kcount_cpu.cpp:367-404); a key absent from the table is absent from the reads once the
 // bucket's last sweep has run (deferred keys are counted in a later sweep), and is finalized here
 // directly (insert_into_local_hashtable, kcount_cpu.cpp:503-522).
-template <int NL, bool CMP, typename K>
+template <int NL, bool CMP, bool WIDE, typename K>
 __device__ void ctg_apply(const CountLds<K> &t, const CountParams &p, uint32_t b, bool last_sweep, bool cold,
                           unsigned long long *s_range) {
   const int tid = threadIdx.x;
@@ -2100,6 +2148,8 @@ __device__ void ctg_apply(const CountLds<K> &t, const CountParams &p, uint32_t b
   constexpr int GS = GS_SLOTS;
   const int ng = t.cap / GS;
   const K *last = t.keys + (NL - 1) * t.cap;
+  // (the sweep's clamps are logged: its end barrier lies before this call; lanes hold distinct keys, so distinct entries)
+  const uint32_t n_clog = WIDE ? (t.clog[CLOG_N] < CLOG_N ? t.clog[CLOG_N] : CLOG_N) : 0u;
   for (uint64_t q = q0 + tid; q < q1; q += C_THREADS) {
     if (p.ctg_done[q]) continue;
     uint64_t key[NL];
@@ -2146,14 +2196,17 @@ __device__ void ctg_apply(const CountLds<K> &t, const CountParams &p, uint32_t b
       bool keep = false;
       if (rc >= 2) {
         const int thr = dyn_threshold(rc, p.dyn_mult, p.dmin_thres);
-        const uint32_t e0 = t.ext[slot], e1 = t.ext[t.cap + slot], e2 = t.ext[2 * t.cap + slot],
-                       e3 = t.ext[3 * t.cap + slot];
+        uint32_t e0 = t.ext[slot], e1 = t.ext[t.cap + slot], e2 = t.ext[2 * t.cap + slot], e3 = t.ext[3 * t.cap + slot];
+        if (WIDE && n_clog) clog_restore(t.clog, n_clog, (uint32_t)slot, e0, e1, e2, e3);
         const char L = ext_choice(e0 & 0xffffu, e0 >> 16, e1 & 0xffffu, e1 >> 16, thr);
         const char R = ext_choice(e2 & 0xffffu, e2 >> 16, e3 & 0xffffu, e3 >> 16, thr);
         keep = L != 'X' && L != 'F' && R != 'X' && R != 'F';
       }
-      if (!keep) {  // {count, left[l] = right[r] = count, from_ctg}; halves >= 0xC000 as 0x8000 (§3.4)
-        const uint32_t h = c >= 0xC000u ? 0x8000u : c;
+      if (!keep) {  // {count, left[l] = right[r] = count, from_ctg}: the depth itself fits a half, and no add follows
+                    // it in this sweep; what the clamps took from the read entry's halves goes with that entry
+        const uint32_t h = c;
+        for (uint32_t i = 0; i < n_clog; i++)
+          if ((t.clog[i] >> 19) == (uint32_t)slot) t.clog[i] = ~0u;
         uint32_t ew[4] = {0, 0, 0, 0};
         if (l < 4) ew[l >> 1] |= h << ((l & 1u) * 16);
         if (r < 4) ew[2 + (r >> 1)] |= h << ((r & 1u) * 16);
@@ -2228,7 +2281,8 @@ __device__ __forceinline__ int count_tid() {
     return (int)threadIdx.x;
 }
 
-template <int NL, bool PACKED, bool CMP>
+// WIDE (CountParams.wide_thr): the instantiation that keeps the clamp log (ext_clamp); the other one carries none of it
+template <int NL, bool PACKED, bool CMP, bool WIDE>
 // (C_SPLIT workgroups per CU must fit its registers together: 4 waves per SIMD, 128 VGPRs each, as one 1024-thread
 // workgroup has)
 __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
@@ -2245,6 +2299,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
   t.keys = (K *)smem;
   t.cnt = (uint32_t *)(t.keys + NL * t.cap);
   t.ext = t.cnt + t.cap;
+  t.clog = WIDE ? (uint32_t *)(smem + count_log_offset(NL, RK::C32)) : nullptr;
   // scalars live after the table in the same dynamic region (count_table_bytes adds 256 bytes)
   unsigned long long *s_u64 = (unsigned long long *)(t.ext + 4 * t.cap);
   unsigned long long &s_gbase = s_u64[0];
@@ -2408,6 +2463,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
       s_next = 2 * (C_THREADS / 64);  // (slots s and 16 + s are wave s's own: already prefetched / next)
     }
     if (tid < C_THREADS / 64) s_wdef[tid] = 0;
+    if (WIDE && tid < CLAMP_LOG) t.clog[tid] = (uint32_t)tid == CLOG_N ? 0u : ~0u;
   };
   if (tid == 0) {
     s_missacc = 0;
@@ -2760,7 +2816,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
     }
     // (a skipped coarse bucket's fine buckets are empty, k_inc_fixup, and its contig k-mers wait for the launch
     // that counts it)
-    if (p.ctg_n && !(p.coarse_skip && p.coarse_skip[b >> p.fine_bits])) ctg_apply<NL, CMP>(t, p, b, last_sweep, cold, s_red);
+    if (p.ctg_n && !(p.coarse_skip && p.coarse_skip[b >> p.fine_bits])) ctg_apply<NL, CMP, WIDE>(t, p, b, last_sweep, cold, s_red);
     {
       // the next bucket's first round, loaded while this one is finalized; unconditional (as the round prefetch:
       // a load under a branch was waited for at once): without a next bucket, or before a re-sweep (which loads
@@ -2832,6 +2888,15 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
 #define MHMKC_FINX 1
 #endif
     const uint32_t n_list = MHMKC_FINX ? (uint32_t)__builtin_amdgcn_readfirstlane(s_fin[0]) : s_fin[0];
+    // the sweep's clamp log (wide thresholds only): its entries' amounts go back into the halves they were taken from
+    uint32_t n_clog = 0;
+    if constexpr (WIDE) {
+      n_clog = (uint32_t)__builtin_amdgcn_readfirstlane(t.clog[CLOG_N]);
+      if (n_clog > CLOG_N) {  // more clamped halves than the log holds: flag the launch (the host refuses the table)
+        if (tid == 0) atomicOr(p.err, 32u);
+        n_clog = CLOG_N;
+      }
+    }
     const uint32_t fin_w0 = (uint32_t)wid * 64u;
     // per listed slot of this thread: sp = slot | output position << 16 (both < 2^16), row = count | L << 16 | R << 24
     uint32_t surv_mask = 0, sp[SPT], row[SPT];
@@ -2850,8 +2915,8 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
         sp[j] = (uint32_t)slot;
         uint16_t c16;
         char L, R_;
-        const uint32_t cw = t.cnt[slot], e0 = t.ext[slot], e1 = t.ext[t.cap + slot], e2 = t.ext[2 * t.cap + slot],
-                       e3 = t.ext[3 * t.cap + slot];
+        const uint32_t cw = t.cnt[slot];
+        uint32_t e0 = t.ext[slot], e1 = t.ext[t.cap + slot], e2 = t.ext[2 * t.cap + slot], e3 = t.ext[3 * t.cap + slot];
         if (KREG && j < KJ) {  // (with the counters: the same round trip)
 #pragma unroll
           for (int w = 0; w < NL; w++) kreg[j < KJ ? j : 0][w] = t.keys[w * t.cap + slot];
@@ -2860,6 +2925,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
         const uint32_t c32 = !cold ? cw
                              : (cw >> 31) ? cw & 0x7fffffffu
                                           : cw + (e0 & 0xffffu) + (e0 >> 16) + (e1 & 0xffffu) + (e1 >> 16);
+        if (WIDE && n_clog) clog_restore(t.clog, n_clog, (uint32_t)slot, e0, e1, e2, e3);
         sv = slot_survives(c32, e0, e1, e2, e3, p, c16, L, R_);
         row[j] = (uint32_t)c16 | (uint32_t)(uint8_t)L << 16 | (uint32_t)(uint8_t)R_ << 24;
       }
@@ -3102,10 +3168,13 @@ static hipError_t do_part_scatter(const PartitionParams &p, hipStream_t s) {
 template <int NL, bool PK, bool CMP = false>
 static hipError_t do_count(const CountParams &p, hipStream_t s) {
   const size_t lds = count_lds_bytes(NL, RecKind<NL, CMP>::C32);
-  hipError_t e = allow_lds(k_count<NL, PK, CMP>, lds);
-  if (e != hipSuccess) return e;
   const uint32_t grid = p.grid && p.grid < p.n_buckets ? p.grid : p.n_buckets;
-  k_count<NL, PK, CMP><<<dim3(grid), dim3(C_THREADS), lds, s>>>(p);
+  hipError_t e = p.wide_thr ? allow_lds(k_count<NL, PK, CMP, true>, lds) : allow_lds(k_count<NL, PK, CMP, false>, lds);
+  if (e != hipSuccess) return e;
+  if (p.wide_thr)
+    k_count<NL, PK, CMP, true><<<dim3(grid), dim3(C_THREADS), lds, s>>>(p);
+  else
+    k_count<NL, PK, CMP, false><<<dim3(grid), dim3(C_THREADS), lds, s>>>(p);
   return hipGetLastError();
 }
 

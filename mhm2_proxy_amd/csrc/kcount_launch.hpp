@@ -146,6 +146,8 @@ struct CountParams {
   int cap;                            // LDS table slots
   int dmin_thres;
   double dyn_mult;                    // 1.0 - DYN_MIN_DEPTH, computed in double on the host
+  int wide_thr;                       // (int)(dyn_mult * 65535) > 0x8000: a threshold can pass the extension counters'
+                                      // clamp target, so every clamp is logged and undone at the decision (§3.4)
   int nlo;                            // output words per key
   uint64_t *out_keys;                 // [out_cap * nlo]
   uint16_t *out_counts;
@@ -273,8 +275,14 @@ __host__ __device__ constexpr size_t count_table_bytes(int nl, bool cmp = false)
 __host__ __device__ constexpr int miss_cap(int nl, bool cmp = false) {
   return (int)(((C_LDS - count_table_bytes(nl, cmp)) / (count_key_bytes(cmp) * nl + 4)) & ~(size_t)63);
 }
-__host__ __device__ constexpr size_t count_lds_bytes(int nl, bool cmp = false) {
+// the clamp log (CountParams.wide_thr, §3.4) follows the miss queues: CLAMP_LOG words (slot << 3 | half) << 16 | the
+// amount the clamps took from that half, saturating; miss_cap rounds down to 64 entries, which leaves the room
+constexpr int CLAMP_LOG = 64;
+__host__ __device__ constexpr size_t count_log_offset(int nl, bool cmp = false) {
   return count_table_bytes(nl, cmp) + (size_t)miss_cap(nl, cmp) * (count_key_bytes(cmp) * nl + 4);
+}
+__host__ __device__ constexpr size_t count_lds_bytes(int nl, bool cmp = false) {
+  return count_log_offset(nl, cmp) + 4 * (size_t)CLAMP_LOG;
 }
 static_assert(count_lds_bytes(1) <= C_LDS && count_lds_bytes(2) <= C_LDS && count_lds_bytes(3) <= C_LDS &&
                   count_lds_bytes(4) <= C_LDS && count_lds_bytes(1, true) <= C_LDS,

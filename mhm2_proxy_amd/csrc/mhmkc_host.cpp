@@ -2438,6 +2438,9 @@ int mhmkc::finish(uint64_t *n_out_ret) {
   // k_count's parameters for the fine buckets of a pass that starts at local coarse bucket c0 (all but the records
   // and the output, which the attempts set)
   int rc_cp = MHMKC_OK;
+  // k_count's err bit 5 (CountParams.wide_thr): a sweep clamped more extension counters than its log holds
+  static const char *const CLAMP_LOG_FULL =
+      "dyn_min_depth < 0.5 with more than 63 saturating extension counters in one hash bucket (DESIGN.md §3.4)";
   auto count_params = [&](uint32_t c0, uint32_t n_fine) {
     mhm::CountParams cp{};
     cp.bucket_base = d_fine_base.as<unsigned long long>();
@@ -2458,6 +2461,7 @@ int mhmkc::finish(uint64_t *n_out_ret) {
     if (g_dbg.cap) cp.cap = std::min<int>(cp.cap, (int)std::max<int64_t>(64, g_dbg.cap) & ~3);
     cp.dmin_thres = dmin;
     cp.dyn_mult = 1.0 - cfg.dyn_min_depth;
+    cp.wide_thr = (int)(cp.dyn_mult * 65535.0) > 0x8000 || dmin > 0x8000;
     cp.nlo = nlo;
     cp.out_cursor = d_out_cursor.as<unsigned long long>();
     cp.stats = d_stats.as<unsigned long long>();
@@ -2537,6 +2541,7 @@ int mhmkc::finish(uint64_t *n_out_ret) {
           (e = hipMemcpyAsync(skip.data(), d_inc_skip.p, no, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
           (e = hipStreamSynchronize(stream)) != hipSuccess)
         return hip_fail(e, "finish");
+      if (errf & 32u) return fail(MHMKC_EUNSUPPORTED, CLAMP_LOG_FULL);
       if (errf & 2u) break;  // (not expected: k_inc_fixup cleared it)
       if (errf & 16u) {  // the output is full: grow it to the rows the cursor counted, count again
         out_cap = cursor_end + cursor_end / 16 + 1024;
@@ -2785,6 +2790,7 @@ int mhmkc::finish(uint64_t *n_out_ret) {
           (e = hipMemcpyAsync(&cursor_end, d_out_cursor.p, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
           (e = hipStreamSynchronize(stream)) != hipSuccess)
         return hip_fail(e, "finish");
+      if (errf & 32u) return fail(MHMKC_EUNSUPPORTED, CLAMP_LOG_FULL);
       if (!(errf & (2u | 16u))) break;
       if (errf & 2u) {  // a capped fine bucket overflowed (skewed input): the pass again with exact bucket sizes
         exact = true;

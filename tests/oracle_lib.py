@@ -101,9 +101,10 @@ def hashref():
 
 
 KCOUNTREF = {None: ROOT / "oracle" / "_ref" / "libkcountref.so",
-             "q25d75": ROOT / "oracle" / "_ref" / "libkcountref_q25d75.so"}
+             "q25d75": ROOT / "oracle" / "_ref" / "libkcountref_q25d75.so",
+             "d25": ROOT / "oracle" / "_ref" / "libkcountref_d25.so"}
 # what each build of the reference was compiled with (KCOUNT_QUAL_CUTOFF, DYN_MIN_DEPTH), oracle/Makefile
-KCOUNTREF_PARAMS = {None: (20, 0.9), "q25d75": (25, 0.75)}
+KCOUNTREF_PARAMS = {None: (20, 0.9), "q25d75": (25, 0.75), "d25": (20, 0.25)}
 _refs = {}
 
 
