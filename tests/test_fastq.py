@@ -69,7 +69,9 @@ def literal_pack(text: bytes, qual_offset: int = 33):
         for ch, q in zip(seq, quals):
             if ch not in _CODE:
                 raise O.FastqError("char", r // 4)
-            qv = min(ord(q) - qual_offset, 31)
+            # packed_reads.cpp:106: quals[i] - qual_offset on `char`, which is signed where the reference runs (x86)
+            qs = ord(q) - 256 if ord(q) >= 0x80 else ord(q)
+            qv = min(qs - qual_offset, 31)
             out.append((_CODE[ch] | ((qv & 0xFF) << 3)) & 0xFF)
         offs.append(len(out))
     if len(lines) % 4:
@@ -133,6 +135,19 @@ def test_oracle_fastq_quality_range(qoff):
     pb, po = O.fastq_pack(t, qoff)
     lb, lo = literal_pack(t, qoff)
     assert (po == lo).all() and (pb == lb).all()
+    # every quality byte value but '\n', 0x80..0xff included (a signed char in the reference), away from the line's
+    # end where the whitespace ones would be trimmed
+    every = bytes(v for v in range(256) if v != 0x0A)
+    t = b"@all\n" + b"ACGTN" * 52 + b"\n+\n" + b"I" * 3 + every + b"I" * 2 + b"\n"
+    pb, po = O.fastq_pack(t, qoff)
+    lb, lo = literal_pack(t, qoff)
+    assert list(po) == list(lo) == [0, 260] and (pb == lb).all()
+    want = [(min((v - 256 if v >= 0x80 else v) - qoff, 31) << 3) & 0xFF for v in every]
+    assert [int(x) & 0xF8 for x in pb[3:258]] == want
+    if qoff == 33:
+        pb, _ = O.fastq_pack(b"@r0\nACGT\n+\n\x80\x81\xa0\xff\n")
+        lb, _ = literal_pack(b"@r0\nACGT\n+\n\x80\x81\xa0\xff\n")
+        assert pb.tobytes() == lb.tobytes() == bytes.fromhex("f801faf3")
 
 
 @pytest.mark.parametrize("name", sorted(BAD))
