@@ -53,6 +53,11 @@ void mhmkc_debug_reset(void);
  * it, streaming stores into a 32-byte aligned dst), 1 the portable 8-bytes-at-a-time path, 2 AVX2 with ordinary stores
  * (MHMKC_EUNSUPPORTED without AVX2). */
 int mhmkc_debug_nib_pack(const uint8_t *src, uint64_t n, uint8_t *dst, int qcut, int mode);
+/* k_count's verdict on one 4-slot group of compact keys, computed on the host by the function the kernels use
+ * (kmer_ops.hpp group_verdict4; no GPU): v the group's four key words (low 6 bits zero, or 0xffffffff for an empty
+ * slot), key the key word looked for. Returns 0..3 the slot that holds the key, 4..7 four plus the first empty slot
+ * when the key is absent, 8 or more for a full group without the key. */
+uint32_t mhmkc_debug_examine4(const uint32_t v[4], uint32_t key);
 
 #ifdef __cplusplus
 }

@@ -56,7 +56,7 @@ ABI_SYMBOLS = [
 UUTIG_MAX_ROUNDS = 48
 SYNTH_SYMBOLS = ["mhmkc_synth_config_init", "mhmkc_synth_genome", "mhmkc_synth_reads"]
 # the test-only entry point (include/mhmkc_debug.h)
-DEBUG_SYMBOLS = ["mhmkc_debug_nib_pack", "mhmkc_debug_reset", "mhmkc_debug_set"]
+DEBUG_SYMBOLS = ["mhmkc_debug_examine4", "mhmkc_debug_nib_pack", "mhmkc_debug_reset", "mhmkc_debug_set"]
 
 
 class MhmkcUutigInfo(C.Structure):

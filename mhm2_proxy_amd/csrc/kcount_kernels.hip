@@ -1850,9 +1850,30 @@ __device__ __forceinline__ bool rest_equal(const CountLds<K> &t, int slot, const
 // Result of looking at one group for key: >= 0 the slot holding it, -1 - i an empty slot i (and the key is
 // not in the group), G_FULL no empty slot and no key, G_BUSY a multi-word key is being written.
 constexpr int G_FULL = -8, G_BUSY = -9;
+// MHMKC_VERDICT (round 8): a 4-slot group of compact keys is examined by arithmetic (group_verdict4, kmer_ops.hpp:
+// m = 0..3 found, 4..7 first empty slot m - 4, >= 8 full) instead of two select chains. The compact cold phase A works
+// on m itself; every other caller of compact keys (lds_insert's re-examination, phase B, the hot phase A, the
+// contig pass) gets the encoding above from m here, in one place. 64-bit key words keep the select chains.
+#ifndef MHMKC_VERDICT
+#define MHMKC_VERDICT 1
+#endif
+// MHMKC_RESOLVE (round 8, needs MHMKC_VERDICT): the compact cold phase A turns verdict and claim result into its
+// add / miss lane masks directly, one conditional region per record (see the round loop).
+#ifndef MHMKC_RESOLVE
+#define MHMKC_RESOLVE 1
+#endif
+// MHMKC_MISSQ1 (round 8): the compact cold phase A checks the miss queue's room once per round, not once per record.
+#ifndef MHMKC_MISSQ1
+#define MHMKC_MISSQ1 0
+#endif
+__device__ __forceinline__ int verdict_code(uint32_t m, int g) {
+  return verdict_found(m) ? 4 * g + (int)m : verdict_empty(m) ? 3 - (int)m : G_FULL;
+}
 template <int NL, int GS, typename K>
 __device__ __forceinline__ int examine_group(const CountLds<K> &t, const uint64_t *key, int g, const K (&v)[GS]) {
   const K kl = (K)key[NL - 1];
+  if constexpr (MHMKC_VERDICT && NL == 1 && GS == 4 && sizeof(K) == 4)
+    return verdict_code(group_verdict4(v[0], v[1], v[2], v[3], (uint32_t)kl), g);
   if constexpr (NL == 1) {  // single-word keys: eight compares and selects, no branch (a key is never EMPTY)
     int r = G_FULL;
 #pragma unroll
@@ -2593,6 +2614,9 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
         //    reads of a batch in flight together), then found records are counted, missed ones listed.
         uint32_t old[R], defer = 0, okm = 0, missm = 0;
         int slot[R], g[R];
+        // compact cold phase A with MHMKC_VERDICT: the verdicts m of group_verdict4 stand in for slot[] (VM)
+        constexpr bool VM = RK::C32 && COLD && MHMKC_VERDICT && GS == 4;
+        uint32_t vm[R];
         if constexpr (RK::C32 && COLD) {
           // compact keys in a cold sweep: the R home groups read back to back and examined, every claim CAS
           // issued before the first one is waited for (the general path below waits for each in turn), then the
@@ -2604,6 +2628,43 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
             g[j] = cmp_group((uint32_t)ck[j][0], kshl, (uint32_t)ng);
             read_group<GS>(last, g[j], gv[j]);
           }
+          if constexpr (VM) {
+            // the verdicts m (group_verdict4) as they are: a claim is 4 <= m < 8, the slot is 4 g + (m & 3) for a found
+            // key and for a claimed slot alike
+#pragma unroll
+            for (int j = 0; j < R; j++)
+              vm[j] = group_verdict4((uint32_t)gv[j][0], (uint32_t)gv[j][1], (uint32_t)gv[j][2], (uint32_t)gv[j][3],
+                                     (uint32_t)ck[j][0]);
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+              res[j] = 0u;
+              if (ce[j] != NONE && verdict_empty(vm[j]))
+                res[j] = atomicCAS((unsigned int *)&last[GS * g[j] + (int)(vm[j] & 3u)], 0xffffffffu, (uint32_t)ck[j][0]);
+            }
+            if constexpr (MHMKC_RESOLVE) {
+              // three lane masks and one conditional region per record, around its two adds: nothing of the general
+              // path's bookkeeping (old counts, the counted mask, slot marks) exists in a cold sweep
+#pragma unroll
+              for (int j = 0; j < R; j++) {
+                const bool won = res[j] == 0xffffffffu || res[j] == (uint32_t)ck[j][0];
+                const bool add = ce[j] != NONE && (verdict_found(vm[j]) || (verdict_empty(vm[j]) && won));
+                if (add) lds_add_nr(t, GS * g[j] + (int)(vm[j] & 3u), ce[j], &s_wave[wid]);
+                missm |= (uint32_t)(ce[j] != NONE && !add) << j;
+              }
+            } else {
+#pragma unroll
+              for (int j = 0; j < R; j++) {
+                int r = verdict_code(vm[j], g[j]);
+                if (r < 0 && r > G_FULL && (res[j] == 0xffffffffu || res[j] == (uint32_t)ck[j][0])) r = GS * g[j] - 1 - r;
+                if (ce[j] == NONE) {
+                } else if (r >= 0) {
+                  lds_add_nr(t, r, ce[j], &s_wave[wid]);
+                } else {
+                  missm |= 1u << j;
+                }
+              }
+            }
+          } else {
 #pragma unroll
           for (int j = 0; j < R; j++) slot[j] = examine_group<NL, GS>(t, ck[j], g[j], gv[j]);
 #pragma unroll
@@ -2627,6 +2688,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
               missm |= 1u << j;
             }
           }
+          }  // select-chain verdicts
         } else {
 #pragma unroll
         for (int j0 = 0; j0 < R; j0 += C_BATCH) {
@@ -2673,6 +2735,32 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
         {
           // this wave's misses join its own queue (ballot + prefix: no LDS atomic); a queue without room for
           // them inserts in place
+          bool listed = false;
+          if constexpr (MHMKC_MISSQ1 && RK::C32 && COLD) {
+            // one room check for the round's misses together (the usual case: the queue is worked off at WQ_THR, far
+            // below MW); a round that would overfill the queue takes the per-record code below unchanged
+            uint64_t bal[R];
+            uint32_t tot = 0;
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+              bal[j] = __ballot((missm >> j) & 1u);
+              tot += (uint32_t)__popcll(bal[j]);
+            }
+            if (wq_n + tot <= (uint32_t)MW) {
+#pragma unroll
+              for (int j = 0; j < R; j++) {
+                if ((missm >> j) & 1u) {
+                  const uint32_t q = wq_base + wq_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[j] >> 32),
+                                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)bal[j], 0u));
+                  s_mkey[q] = (K)ck[j][0];
+                  s_me[q] = ce[j];
+                }
+                wq_n += (uint32_t)__popcll(bal[j]);
+              }
+              listed = true;
+            }
+          }
+          if (!listed) {
 #pragma unroll
           for (int j = 0; j < R; j++) {
             const bool mj = (missm >> j) & 1u;
@@ -2689,7 +2777,8 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
               }
               wq_n += tot;
             } else if (mj) {
-              const int r = lds_insert<NL, GS>(t, ck[j], g[j], slot[j]);
+              // (VM: the verdict in lds_insert's encoding; a lost claim re-examines its group there)
+              const int r = lds_insert<NL, GS>(t, ck[j], g[j], VM ? verdict_code(vm[j], g[j]) : slot[j]);
               if (r == -1) defer |= 1u << j;
               if (r == -2) s_err = 1;
               slot[j] = r;
@@ -2702,6 +2791,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
               }
             }
           }
+          }  // per-record room checks
         }
 #pragma unroll
         for (int j = 0; j < R; j++)

@@ -329,6 +329,33 @@ MHM_HD uint64_t minimizer_fast(const uint64_t *w, int k, int m) {
 // Packed-record mode: the 6-bit ext code fits into the zero low bits of the last key word.
 MHM_HD bool ext_packs(int k, int nl) { return 2 * (k - 32 * (nl - 1)) + EXT_BITS <= 64; }
 
+// Verdict of one 4-slot probe group of compact keys (32-bit key words, k_count's table) for the key word kl:
+//   0..3  slot m of the group holds the key;
+//   4..7  the key is not in the group and slot m - 4 is its first empty slot;
+//   >= 8  neither the key nor an empty slot (a full group).
+// A compact key word has its low EXT_BITS bits zero and EMPTY is all ones, so a slot that is not the key differs
+// from it in a bit >= EXT_BITS (another key) or in all the low bits (EMPTY), and a slot that is not EMPTY has all the
+// low bits of its complement set. Hence
+//   t_i = (v[i] ^ kl) | i         == i      iff slot i holds the key, else >= 2^EXT_BITS - 1,
+//   e_i = ~v[i]       | (4 + i)   == 4 + i  iff slot i is empty,      else >= 2^EXT_BITS - 1,
+// and the minimum of the eight is the verdict: the key (t < 4) before any empty slot (e >= 4), the lowest index
+// first among each; nothing depends on the groups filling front to back. The index goes in with an OR, not an add:
+// (EMPTY ^ 0) + i and ~0 + 4 + i wrap around to small values for the key word 0, a valid key (poly-A).
+// Eight bit operations and four minima, three deep, no compare and no select (the select chains it replaces went
+// through the condition register one after the other).
+static_assert(EXT_BITS >= 3 && (1u << EXT_BITS) - 1 >= 8, "a mismatching slot must give a value of at least 8");
+constexpr uint32_t VERDICT_FULL = 8;
+// the two boundaries of a verdict m, spelled once
+MHM_HD bool verdict_found(uint32_t m) { return m < 4u; }                        // slot m holds the key
+MHM_HD bool verdict_empty(uint32_t m) { return m - 4u < VERDICT_FULL - 4u; }    // absent, slot m - 4 is empty
+MHM_HD uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+MHM_HD uint32_t group_verdict4(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t kl) {
+  const uint32_t t0 = v0 ^ kl, t1 = (v1 ^ kl) | 1u, t2 = (v2 ^ kl) | 2u, t3 = (v3 ^ kl) | 3u;
+  const uint32_t e0 = ~v0 | 4u, e1 = ~v1 | 5u, e2 = ~v2 | 6u, e3 = ~v3 | 7u;
+  const uint32_t a = umin32(umin32(t0, t1), t2), b = umin32(umin32(t3, e0), e1), c = umin32(umin32(e2, e3), a);
+  return umin32(b, c);
+}
+
 // get_ext of the reference (src/kcount/kcount_cpu.cpp:173-182): 'X' when the top count is below the
 // dynamic threshold, 'F' when the runner-up reaches it, otherwise the (then unique) top base.
 // thr = max((int)((1.0 - DYN_MIN_DEPTH) * count), dmin_thres).

@@ -4447,4 +4447,6 @@ int mhmkc_debug_nib_pack(const uint8_t *src, uint64_t n, uint8_t *dst, int qcut,
   return MHMKC_OK;
 }
 
+uint32_t mhmkc_debug_examine4(const uint32_t v[4], uint32_t key) { return mhm::group_verdict4(v[0], v[1], v[2], v[3], key); }
+
 }  // extern "C"
