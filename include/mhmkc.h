@@ -252,6 +252,33 @@ int mhmkc_fastq_fetch(mhmkc_t h, uint8_t *bytes, uint64_t *offsets);
  * equals a single rank given the concatenation. */
 int mhmkc_add_ctgs(mhmkc_t h, const char *seqs, const uint64_t *seq_offsets, const uint16_t *depths, uint64_t n_ctgs);
 
+/* mhmkc_add_ctgs with device arrays (add_ctg_kmers, src/kcount/kcount.cpp:100-138; Contig::get_uint16_t_depth,
+ * src/contigs.hpp:65): d_seqs holds the contigs' ASCII bases back to back, d_seq_offsets n_ctgs+1 offsets, d_depths one
+ * depth per contig. n_bases sizes the handle's buffers without a round trip and must equal d_seq_offsets[n_ctgs] (the
+ * device checks it). The inputs are read during the call only, on the handle's stream (written on another stream:
+ * mhmkc_wait_stream first), and converted into the handle's own device buffers: the caller may overwrite or free them
+ * once the call returns. The call waits for the device once, on a few words that name what is wrong with the input.
+ *   MHMKC_DEPTH_U16: uint16_t depths, taken as they are. MHMKC_DEPTH_F64: double, a Contig::depth as
+ *   mhmkc_uutigs_device gives it, converted as the reference does: (uint16_t)(depth > 65535 ? 65535 : depth), which
+ *   truncates toward zero and turns +inf into 65535. 0 counts as 1 in both. A NaN or negative depth has no defined
+ *   conversion there: MHMKC_EINVAL, the message names the first such contig.
+ *   MHMKC_EBADCHAR: a byte outside ACGTNacgtn (the message names the first position, as mhmkc_add_ctgs does).
+ *   MHMKC_EINVAL: offsets[0] != 0, decreasing offsets, a wrong n_bases, a null pointer with n_ctgs > 0, or 2^32-1 or more
+ *   contig k-mers in the round. MHMKC_ESTATE after finish. A failed call adds nothing to the round.
+ * Contigs are applied in the order they were added, whichever of mhmkc_add_ctgs, mhmkc_add_ctgs_device and
+ * mhmkc_add_ctgs_from added them. From the first device add of a round on, the round's contigs are kept on the device
+ * (counted in mhmkc_stats.device_bytes[_peak]) until mhmkc_reset or mhmkc_destroy; host adds that follow are uploaded
+ * at once. Single-rank handles only (MHMKC_EUNSUPPORTED with n_ranks > 1, checked before the state). */
+enum { MHMKC_DEPTH_U16 = 0, MHMKC_DEPTH_F64 = 1 };
+int mhmkc_add_ctgs_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const void *d_depths,
+                          int depth_type, uint64_t n_ctgs, uint64_t n_bases);
+/* The uutigs of the finished handle src as h's contigs, without leaving the device: mhmkc_add_ctgs_device on
+ * mhmkc_uutigs_device(src) with MHMKC_DEPTH_F64 (the step from one contigging round to the next k,
+ * src/contigging.cpp:93-158; k may differ between the handles). The uutigs are built first if src has none yet; src's
+ * stream is ordered before h's by an event. src not finished: MHMKC_ESTATE; another device: MHMKC_EINVAL; src with
+ * n_ranks > 1: mhmkc_uutigs's MHMKC_EUNSUPPORTED. The failure's text is in mhmkc_last_error(h). */
+int mhmkc_add_ctgs_from(mhmkc_t h, mhmkc_t src);
+
 /* The depth threshold of the finish: the reference's global _dmin_thres (src/kcount/kmer_dht.hpp:57), which
  * analyze_kmers sets (src/kcount/kcount.cpp:145) after the KmerDHT was built and get_ext reads at finish
  * (src/kcount/kcount_cpu.cpp:178). Starts as mhmkc_config.dmin_thres; takes effect at the next finish. */

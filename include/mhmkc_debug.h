@@ -44,7 +44,9 @@ extern "C" {
  *   merge_grid    at most v workgroups (four waves each, one read pair per wave and turn) for k_fq_merge, both
  *                 instances, and k_fq_merge_pack (fastq.hip), so that a wave merges and packs several pairs in turn on a
  *                 small batch: the prefetched next descriptor, the reuse of the wave's LDS after another pair (0: the
- *                 launches' own grids) */
+ *                 launches' own grids)
+ *   ctg_pack_grid at most v workgroups for k_ctg_pack (kcount_ctgin.hip: mhmkc_add_ctgs_device, mhmkc_add_ctgs_from), so
+ *                 that a lane converts several 16-byte vectors in turn on a small batch (0: the launch's own grid) */
 int mhmkc_debug_set(const char *knob, int64_t value);
 /* Every knob back to its default. */
 void mhmkc_debug_reset(void);

@@ -970,6 +970,14 @@ class HashTableInserter {
       ctg_depths_.clear();
     }
   }
+  // the previous round's uutigs as this round's contigs, handed over on the device (mhmkc_add_ctgs_from: the `ctgs` of
+  // contigging(), src/contigging.cpp:93-158, never leave HBM). prev must be finished; its uutigs are built if it has
+  // none yet. Buffered supermers go first, so that the order of the calls is the order the contigs are applied in.
+  template <int PREV_MAX_K>
+  void add_ctgs_from(HashTableInserter<PREV_MAX_K> &prev) {
+    flush_inserts();
+    check(mhmkc_add_ctgs_from(h_, prev.handle()), h_, "mhmkc_add_ctgs_from");
+  }
   // kcount_cpu.cpp:490-528 (get_ext reads the global _dmin_thres at this point, :178)
   void insert_into_local_hashtable(KmerMap<MAX_K> &local_kmers) {
     flush_inserts();
@@ -1060,6 +1068,10 @@ class KmerDHT {
   void add_fastq(const std::string &text) { ht_inserter.add_fastq(text); }
   void add_fastq_file(const std::string &path, bool pairs = false) { ht_inserter.add_fastq_file(path, pairs); }
   void flush_updates() { ht_inserter.flush_inserts(); }
+  template <int PREV_MAX_K>
+  void add_ctgs_from(KmerDHT<PREV_MAX_K> &prev) {
+    ht_inserter.add_ctgs_from(prev.inserter());
+  }
   void finish_updates() { ht_inserter.insert_into_local_hashtable(local_kmers); }
   // fill the local KmerMap from a finished table in mhmkc_fetch's layout (n_longs = N_LONGS words per key)
   void load_table(const uint64_t *keys, const uint16_t *counts, const char *left, const char *right, uint64_t n) {
@@ -1149,6 +1161,26 @@ void analyze_kmers(unsigned kmer_len, unsigned /*prev_kmer_len*/, int qual_offse
     sbi.done_processing(kmer_dht);
     kmer_dht.flush_updates();
   }
+  kmer_dht.finish_updates();
+  if (dump_kmers) kmer_dht.dump_kmers();
+}
+
+// The same with the previous round's KmerDHT in place of its contigs: add_ctg_kmers (kcount.cpp:100-138) over the uutigs
+// of prev_dht's finished table (traverse_debruijn_graph at one rank), which stay on the device between the rounds
+// (mhmkc_add_ctgs_from). The reads come first and the contig pass runs at finish, as above; the table equals
+// traverse_debruijn_graph_device(prev_dht) -> Contigs -> analyze_kmers(ctgs). Single rank.
+template <int MAX_K, int PREV_MAX_K>
+void analyze_kmers(unsigned kmer_len, unsigned /*prev_kmer_len*/, int qual_offset,
+                   std::vector<PackedReads *> &packed_reads_list, int dmin_thres, KmerDHT<PREV_MAX_K> &prev_dht,
+                   KmerDHT<MAX_K> &kmer_dht, bool dump_kmers) {
+  if (kmer_len != Kmer<MAX_K>::get_k()) die("kmer_len differs from Kmer<MAX_K>::get_k()");
+  _dmin_thres = dmin_thres;  // kcount.cpp:145
+  for (auto *pr : packed_reads_list) {
+    if (pr->get_qual_offset() != qual_offset) die("qual_offset mismatch");
+    kmer_dht.add_packed_reads(*pr);
+  }
+  kmer_dht.flush_updates();
+  kmer_dht.add_ctgs_from(prev_dht);
   kmer_dht.finish_updates();
   if (dump_kmers) kmer_dht.dump_kmers();
 }

@@ -52,7 +52,9 @@ ABI_SYMBOLS = [
     "mhmkc_lookup", "mhmkc_lookup_device", "mhmkc_dbjg_links", "mhmkc_dbjg_links_device",
     "mhmkc_uutigs", "mhmkc_uutigs_fetch", "mhmkc_uutigs_device", "mhmkc_uutig_rows", "mhmkc_uutig_rows_device",
     "mhmkc_uutigs_info",
+    "mhmkc_add_ctgs_device", "mhmkc_add_ctgs_from",
 ]
+MHMKC_DEPTH_U16, MHMKC_DEPTH_F64 = 0, 1
 UUTIG_MAX_ROUNDS = 48
 SYNTH_SYMBOLS = ["mhmkc_synth_config_init", "mhmkc_synth_genome", "mhmkc_synth_reads"]
 # the test-only entry point (include/mhmkc_debug.h)
@@ -229,6 +231,8 @@ def lib() -> C.CDLL:
     L.mhmkc_add_reads_device.argtypes = [VP, VP, VP, U64, U64]
     L.mhmkc_add_seqs.argtypes = [VP, C.c_char_p, VP, U64, C.c_uint16]
     L.mhmkc_add_ctgs.argtypes = [VP, C.c_char_p, VP, VP, U64]
+    L.mhmkc_add_ctgs_device.argtypes = [VP, VP, VP, VP, C.c_int, U64, U64]
+    L.mhmkc_add_ctgs_from.argtypes = [VP, VP]
     L.mhmkc_add_fastq.argtypes = [VP, C.c_char_p, U64]
     L.mhmkc_add_fastq_device.argtypes = [VP, VP, U64]
     L.mhmkc_add_fastq_pairs.argtypes = [VP, C.c_char_p, U64]

@@ -206,6 +206,28 @@ hipError_t ctg_prepare(const CtgView &cv, int k, int nl, bool mixed, int qual_cu
                        uint64_t *const out_keys[4], uint32_t *out_state, uint32_t *out_bucket, uint64_t *n_out,
                        unsigned int *err, hipStream_t s);
 
+// Contigs that are already on the device (kcount_ctgin.hip: mhmkc_add_ctgs_device, mhmkc_add_ctgs_from): ASCII bases,
+// offsets and depths are converted into the arrays of a CtgView, appended to what the round holds. What the kernels
+// find goes to a mailbox the host reads once per call.
+struct CtgInBox {
+  unsigned long long bad_pos;    // first byte outside ACGTNacgtn (~0: none)
+  unsigned long long bad_off;    // first contig whose end offset is below its start (~0: none)
+  unsigned long long bad_depth;  // first contig with a NaN or negative depth (~0: none)
+  unsigned long long windows;    // the round's counted windows with this batch
+  unsigned long long first_off, last_off;  // offs[0], offs[n_ctgs]
+};
+// Workgroups of the packing kernel's grid-stride launch. The test knob ctg_pack_grid (include/mhmkc_debug.h) caps them at
+// ctg_pack_grid_cap, so that a lane takes several vectors in turn on a small batch; 0, the product's value: its own grid.
+inline unsigned ctg_pack_grid_cap = 0;
+size_t ctgin_tmp_bytes(uint64_t n_ctgs);
+// seqs[n_bases], offs[n_ctgs + 1], depths[n_ctgs] (double when depth_f64, else uint16_t) -> out_bytes[n_bases] (the
+// PackedRead bytes, at any byte address), out_offs[0..n_ctgs] = b0 + offs, out_win[0..n_ctgs] = w0 + the windows before
+// each contig, out_depth[n_ctgs]; out_offs / out_win / out_depth point at the round's first free entry. Nothing is read
+// through offs but the offsets themselves, so a bad CSR costs no out-of-bounds access: the mailbox names it.
+hipError_t launch_ctgin(const char *seqs, const uint64_t *offs, const void *depths, bool depth_f64, uint64_t n_ctgs,
+                        uint64_t n_bases, int k, uint64_t b0, uint64_t w0, uint8_t *out_bytes, uint64_t *out_offs,
+                        uint64_t *out_win, uint16_t *out_depth, void *tmp, size_t tmp_bytes, CtgInBox *box, hipStream_t s);
+
 enum {
   STAT_DISTINCT = 0,
   STAT_NOUT = 1,

@@ -385,4 +385,46 @@ MHM_HD int dyn_threshold(uint32_t count16, double dyn_mult, int dmin_thres) {
   return t > dmin_thres ? t : dmin_thres;
 }
 
+// PackedRead byte of a contig character (the contig pass's input, kcount_ctg.hip): code A0 C1 G2 T3 N4, quality 31 in
+// bits 3.. for an uppercase letter and 0 for a lowercase one (get_kmers_and_exts: quals[i] = isupper,
+// src/kcount/kcount_cpu.cpp:309-313). -1: not one of ACGTNacgtn (insert_supermer DIEs, :452-458).
+MHM_HD int ctg_byte(uint8_t c) {
+  int code;
+  switch (c | 0x20) {
+    case 'a': code = 0; break;
+    case 'c': code = 1; break;
+    case 'g': code = 2; break;
+    case 't': code = 3; break;
+    case 'n': code = 4; break;
+    default: return -1;
+  }
+  return (c & 0xDF) != c ? code : code | (31 << 3);
+}
+
+// 0x80 in every byte lane of v that equals c (exact: no carry leaves a lane)
+MHM_HD uint32_t swar_eq4(uint32_t v, uint32_t c) {
+  const uint32_t y = v ^ (c * 0x01010101u);
+  return ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y) & 0x80808080u;
+}
+
+// ctg_byte for the four characters of x at once; *bad gets 0x80 in the lane of every character ctg_byte refuses (that
+// lane of the result means nothing). The letters differ in bits 1-3: A 000, C 001, G 011, T 010, N 111, so bits 2:1 as a
+// Gray code give A0 C1 G2 T3 (N as G), bit 3 marks N, and bit 5 clear is uppercase.
+MHM_HD uint32_t ctg_pack4(uint32_t x, uint32_t *bad) {
+  const uint32_t u = x | 0x20202020u;
+  *bad = (swar_eq4(u, 'a') | swar_eq4(u, 'c') | swar_eq4(u, 'g') | swar_eq4(u, 't') | swar_eq4(u, 'n')) ^ 0x80808080u;
+  const uint32_t g = (x >> 1) & 0x03030303u;
+  const uint32_t isn = (x >> 3) & 0x01010101u;
+  const uint32_t code = (g ^ ((g >> 1) & 0x01010101u)) ^ (isn * 6u);
+  const uint32_t upper = (~x >> 5) & 0x01010101u;
+  return code | (upper * 0xF8u);
+}
+
+// Contig::get_uint16_t_depth of a Contig::depth (src/contigs.hpp:65): (uint16_t)(depth > 65535 ? 65535 : depth), that
+// is truncation toward zero, +inf -> 65535. A NaN or a negative depth has no defined conversion there: *ok = false.
+MHM_HD uint16_t ctg_depth_u16(double depth, bool *ok) {
+  *ok = depth >= 0.0;
+  return *ok ? (uint16_t)(depth > 65535 ? 65535 : depth) : (uint16_t)0;
+}
+
 }  // namespace mhm

@@ -71,6 +71,7 @@ struct DebugKnobs {
   // of kcount_query.hip and kcount_uutig.hip read it: mhm::query_grid_cap (kcount_launch.hpp)
   // merge_grid, the most workgroups of the read-pair merge's launches (0: their own grids), likewise lives where
   // fastq.hip's launches read it: mhm::merge_grid_cap (kcount_launch.hpp)
+  // ctg_pack_grid, the most workgroups of the contig packing kernel (0: its own grid): mhm::ctg_pack_grid_cap
 };
 DebugKnobs g_dbg;
 
@@ -554,6 +555,24 @@ struct mhmkc {
   DevBuf d_ctg_keys[4];
   uint64_t ctg_n = 0;  // folded contig k-mers of the last finish
   int prepare_ctgs();
+  // contigs given on the device (mhmkc_add_ctgs_device, mhmkc_add_ctgs_from). From the round's first
+  // such add on (pc_on) its contigs live in d_pc_*, in the layout prepare_ctgs hands to the contig pass: that add moves
+  // what the host vectors above hold there, a later host add is uploaded at once, so the order of the adds is the order
+  // of the arrays. pc_n contigs, pc_nb bytes, pc_w counted windows; the buffers grow keeping their contents.
+  bool pc_on = false;
+  uint64_t pc_n = 0, pc_nb = 0, pc_w = 0;
+  DevBuf d_pc_bytes, d_pc_offs, d_pc_win, d_pc_depth, d_pc_tmp, d_pc_box;
+  int pc_reserve(uint64_t more_ctgs, uint64_t more_bytes);
+  int pc_begin();
+  int pc_append_host(const uint8_t *bytes, uint64_t nb, const uint64_t *ends, const uint64_t *wends, const uint16_t *depth,
+                     uint64_t n);
+  int add_ctgs_dev(const char *d_seqs, const uint64_t *d_offs, const void *d_depths, int depth_type, uint64_t n_ctgs,
+                   uint64_t n_bases);
+  void pc_drop() {
+    pc_on = false;
+    pc_n = pc_nb = pc_w = 0;
+    for (DevBuf *b : {&d_pc_bytes, &d_pc_offs, &d_pc_win, &d_pc_depth, &d_pc_tmp, &d_pc_box}) b->release();
+  }
 
   std::string err;
   bool finished = false;
@@ -1859,18 +1878,25 @@ int mhmkc::prepare_ctgs() {
     }
     cb_ = &ctg_gbytes, co = &ctg_goffs, cw = &ctg_gwin, cd = &ctg_gdepth;
   }
-  const uint64_t W = cw->back();
+  const uint64_t W = pc_on ? pc_w : cw->back();
   if (!W) return MHMKC_OK;
   hipError_t e;
-  const uint64_t nc = cd->size();
-  if ((e = grow(d_ctg_bytes, cb_->size() + 64)) != hipSuccess || (e = grow(d_ctg_offs, (nc + 1) * 8)) != hipSuccess ||
-      (e = grow(d_ctg_win, (nc + 1) * 8)) != hipSuccess || (e = grow(d_ctg_depth, nc * 2 + 2)) != hipSuccess)
-    return hip_fail(e, "contig staging");
-  if ((e = hipMemcpyAsync(d_ctg_bytes.p, cb_->data(), cb_->size(), hipMemcpyHostToDevice, stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_ctg_offs.p, co->data(), (nc + 1) * 8, hipMemcpyHostToDevice, stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_ctg_win.p, cw->data(), (nc + 1) * 8, hipMemcpyHostToDevice, stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_ctg_depth.p, cd->data(), nc * 2, hipMemcpyHostToDevice, stream)) != hipSuccess)
-    return hip_fail(e, "contig H2D");
+  const uint64_t nc = pc_on ? pc_n : cd->size();
+  // the round's contigs are on the device already (single rank): the contig pass reads them where they are, every time
+  mhm::CtgView cv{d_pc_bytes.as<uint8_t>(), d_pc_offs.as<uint64_t>(), d_pc_depth.as<uint16_t>(), d_pc_win.as<uint64_t>(),
+                  nc, W};
+  if (!pc_on) {
+    if ((e = grow(d_ctg_bytes, cb_->size() + 64)) != hipSuccess || (e = grow(d_ctg_offs, (nc + 1) * 8)) != hipSuccess ||
+        (e = grow(d_ctg_win, (nc + 1) * 8)) != hipSuccess || (e = grow(d_ctg_depth, nc * 2 + 2)) != hipSuccess)
+      return hip_fail(e, "contig staging");
+    if ((e = hipMemcpyAsync(d_ctg_bytes.p, cb_->data(), cb_->size(), hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_ctg_offs.p, co->data(), (nc + 1) * 8, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_ctg_win.p, cw->data(), (nc + 1) * 8, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_ctg_depth.p, cd->data(), nc * 2, hipMemcpyHostToDevice, stream)) != hipSuccess)
+      return hip_fail(e, "contig H2D");
+    cv = mhm::CtgView{d_ctg_bytes.as<uint8_t>(), d_ctg_offs.as<uint64_t>(), d_ctg_depth.as<uint16_t>(),
+                      d_ctg_win.as<uint64_t>(), nc, W};
+  }
   const size_t sb = mhm::ctg_scratch_bytes(W, nl);
   if ((e = grow(d_ctg_scratch, sb)) != hipSuccess) return hip_fail(e, "contig scratch");
   uint64_t *keys[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1881,8 +1907,6 @@ int mhmkc::prepare_ctgs() {
   if ((e = grow(d_ctg_state, W * 4)) != hipSuccess || (e = grow(d_ctg_bucket, W * 4)) != hipSuccess ||
       (e = grow(d_ctg_done, W)) != hipSuccess)
     return hip_fail(e, "contig entries");
-  mhm::CtgView cv{d_ctg_bytes.as<uint8_t>(), d_ctg_offs.as<uint64_t>(), d_ctg_depth.as<uint16_t>(),
-                  d_ctg_win.as<uint64_t>(), nc, W};
   prof_begin(MHMKC_STAGE_OTHER);
   // the synchronous copies above keep the host vectors alive long enough: ctg_prepare waits for its
   // fold count before returning
@@ -3188,6 +3212,7 @@ void mhmkc_destroy(mhmkc_t h) {
                      &h->d_ctg_state, &h->d_ctg_bucket, &h->d_ctg_done, &h->d_ctg_keys[0], &h->d_ctg_keys[1],
                      &h->d_ctg_keys[2], &h->d_ctg_keys[3]};
   for (DevBuf *b : cbufs) b->release();
+  h->pc_drop();
   h->x_send.release();
   h->x_recv.release();
   h->fq_file_buf.release();
@@ -3701,6 +3726,28 @@ int mhmkc_add_ctgs(mhmkc_t h, const char *seqs, const uint64_t *offs, const uint
   if (h->finished) return h->fail(MHMKC_ESTATE, "handle already finished; call mhmkc_reset first");
   if (offs[0] != 0) return h->fail(MHMKC_EINVAL, "seq_offsets[0] must be 0");
   const uint64_t k = (uint64_t)h->k;
+  if (h->pc_on) {  // the round's contigs are on the device: this batch follows them there, now
+    uint64_t W = h->pc_w;
+    std::vector<uint64_t> ends(n_ctgs), wends(n_ctgs);
+    for (uint64_t i = 0; i < n_ctgs; i++) {
+      if (offs[i + 1] < offs[i]) return h->fail(MHMKC_EINVAL, "seq_offsets must be non-decreasing");
+      const uint64_t L = offs[i + 1] - offs[i];
+      W += L >= k + 2 ? L - k - 1 : 0;
+      ends[i] = h->pc_nb + offs[i + 1];
+      wends[i] = W;
+    }
+    if (W >= 0xffffffffull) return h->fail(MHMKC_EINVAL, "at most 2^32-1 contig k-mers per round");
+    const uint64_t n = offs[n_ctgs];
+    std::vector<uint8_t> bytes(n);
+    for (uint64_t i = 0; i < n; i++) {
+      const int b = seq_byte(seqs[i]);
+      if (b < 0)
+        return h->fail(MHMKC_EBADCHAR, "bad char '%c' (%d) in contig position %llu", seqs[i], (int)seqs[i],
+                       (unsigned long long)i);
+      bytes[i] = (uint8_t)b;
+    }
+    return h->pc_append_host(bytes.data(), n, ends.data(), wends.data(), depths, n_ctgs);
+  }
   uint64_t W = h->ctg_win.back();
   for (uint64_t i = 0; i < n_ctgs; i++) {
     if (offs[i + 1] < offs[i]) return h->fail(MHMKC_EINVAL, "seq_offsets must be non-decreasing");
@@ -3729,6 +3776,143 @@ int mhmkc_add_ctgs(mhmkc_t h, const char *seqs, const uint64_t *offs, const uint
     h->ctg_depth.push_back(depths[i]);
   }
   return MHMKC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// contigs given on the device (kcount_ctgin.hip)
+
+int mhmkc::pc_reserve(uint64_t more_ctgs, uint64_t more_bytes) {
+  const uint64_t nc = pc_n + more_ctgs;
+  hipError_t e;
+  // (+ 64 bytes: the pad the host route's staging buffer has)
+  // a later add of the round that does not fit takes half as much again, so that many small adds copy little
+  auto keep = [&](DevBuf &b, size_t used, size_t need) {
+    return need <= b.cap && b.p ? hipSuccess : grow_keep(b, used, b.p ? need + need / 2 : need);
+  };
+  if ((e = keep(d_pc_bytes, pc_nb, pc_nb + more_bytes + 64)) != hipSuccess ||
+      (e = keep(d_pc_offs, (pc_n + 1) * 8, (nc + 1) * 8)) != hipSuccess ||
+      (e = keep(d_pc_win, (pc_n + 1) * 8, (nc + 1) * 8)) != hipSuccess ||
+      (e = keep(d_pc_depth, pc_n * 2, nc * 2 + 2)) != hipSuccess)
+    return hip_fail(e, "device contigs");
+  return MHMKC_OK;
+}
+
+// The round's first device add: what the host adds have gathered so far goes to the device, in its order.
+int mhmkc::pc_begin() {
+  hipError_t e;
+  int rc;
+  if ((e = d_pc_offs.ensure(8)) != hipSuccess || (e = d_pc_win.ensure(8)) != hipSuccess ||
+      (e = hipMemsetAsync(d_pc_offs.p, 0, 8, stream)) != hipSuccess ||
+      (e = hipMemsetAsync(d_pc_win.p, 0, 8, stream)) != hipSuccess)
+    return hip_fail(e, "device contigs");
+  pc_on = true;
+  if ((rc = pc_append_host(ctg_bytes.data(), ctg_bytes.size(), ctg_offs.data() + 1, ctg_win.data() + 1, ctg_depth.data(),
+                           ctg_depth.size()))) {
+    pc_drop();  // (the host vectors still hold the round)
+    return rc;
+  }
+  std::vector<uint8_t>().swap(ctg_bytes);
+  ctg_offs.assign(1, 0);
+  ctg_win.assign(1, 0);
+  ctg_depth.clear();
+  return MHMKC_OK;
+}
+
+// n contigs in the contig pass's layout: ends / wends are their end offsets and window-prefix ends in the round.
+int mhmkc::pc_append_host(const uint8_t *bytes, uint64_t nb, const uint64_t *ends, const uint64_t *wends,
+                          const uint16_t *depth, uint64_t n) {
+  if (!n) return MHMKC_OK;
+  int rc = pc_reserve(n, nb);
+  if (rc) return rc;
+  hipError_t e = hipSuccess;
+  if (nb) e = hipMemcpyAsync(d_pc_bytes.as<uint8_t>() + pc_nb, bytes, nb, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_pc_offs.as<uint64_t>() + pc_n + 1, ends, n * 8, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_pc_win.as<uint64_t>() + pc_n + 1, wends, n * 8, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_pc_depth.as<uint16_t>() + pc_n, depth, n * 2, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (the caller's arrays may go once this returns)
+  if (e != hipSuccess) return hip_fail(e, "contig H2D");
+  pc_n += n;
+  pc_nb += nb;
+  pc_w = wends[n - 1];
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return MHMKC_OK;
+}
+
+int mhmkc::add_ctgs_dev(const char *d_seqs, const uint64_t *d_offs, const void *d_depths, int depth_type, uint64_t n_ctgs,
+                        uint64_t n_bases) {
+  if (!n_ctgs) return n_bases ? fail(MHMKC_EINVAL, "n_bases = %llu with no contigs", (unsigned long long)n_bases) : MHMKC_OK;
+  int rc;
+  if (!pc_on && (rc = pc_begin())) return rc;
+  if ((rc = pc_reserve(n_ctgs, n_bases))) return rc;
+  hipError_t e;
+  const size_t tb = mhm::ctgin_tmp_bytes(n_ctgs);
+  if ((e = grow(d_pc_tmp, tb)) != hipSuccess || (e = grow(d_pc_box, sizeof(mhm::CtgInBox))) != hipSuccess)
+    return hip_fail(e, "device contigs scratch");
+  mhm::CtgInBox box;
+  prof_begin(MHMKC_STAGE_OTHER);
+  e = mhm::launch_ctgin(d_seqs, d_offs, d_depths, depth_type == MHMKC_DEPTH_F64, n_ctgs, n_bases, k, pc_nb, pc_w,
+                        d_pc_bytes.as<uint8_t>() + pc_nb, d_pc_offs.as<uint64_t>() + pc_n, d_pc_win.as<uint64_t>() + pc_n,
+                        d_pc_depth.as<uint16_t>() + pc_n, d_pc_tmp.p, tb, d_pc_box.as<mhm::CtgInBox>(), stream);
+  prof_end();
+  // the call's one host synchronisation: the mailbox. Until pc_n / pc_nb / pc_w move, what the kernels wrote past them is
+  // not part of the round, so every failure below leaves the round as it was.
+  if (e == hipSuccess) e = hipMemcpyAsync(&box, d_pc_box.p, sizeof box, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "device contigs");
+  if (box.first_off != 0) return fail(MHMKC_EINVAL, "seq_offsets[0] must be 0");
+  if (box.bad_off != ~0ull)
+    return fail(MHMKC_EINVAL, "seq_offsets must be non-decreasing (contig %llu)", (unsigned long long)box.bad_off);
+  if (box.last_off != n_bases)
+    return fail(MHMKC_EINVAL, "n_bases = %llu, seq_offsets[n_ctgs] = %llu", (unsigned long long)n_bases,
+                (unsigned long long)box.last_off);
+  if (box.windows >= 0xffffffffull) return fail(MHMKC_EINVAL, "at most 2^32-1 contig k-mers per round");
+  if (box.bad_pos != ~0ull) {
+    unsigned char c = 0;  // (the message's character: one more byte, on the failure path only)
+    (void)hipMemcpyAsync(&c, d_seqs + box.bad_pos, 1, hipMemcpyDeviceToHost, stream);
+    (void)hipStreamSynchronize(stream);
+    return fail(MHMKC_EBADCHAR, "bad char '%c' (%d) in contig position %llu", c, (int)c, (unsigned long long)box.bad_pos);
+  }
+  if (box.bad_depth != ~0ull)
+    return fail(MHMKC_EINVAL, "contig %llu: a NaN or negative depth has no uint16 conversion",
+                (unsigned long long)box.bad_depth);
+  pc_n += n_ctgs;
+  pc_nb += n_bases;
+  pc_w = box.windows;
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return MHMKC_OK;
+}
+
+int mhmkc_add_ctgs_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const void *d_depths, int depth_type,
+                          uint64_t n_ctgs, uint64_t n_bases) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks > 1) return h->fail(MHMKC_EUNSUPPORTED, "device contigs: single-rank handles only");
+  if (h->finished) return h->fail(MHMKC_ESTATE, "handle already finished; call mhmkc_reset first");
+  if (depth_type != MHMKC_DEPTH_U16 && depth_type != MHMKC_DEPTH_F64) return h->fail(MHMKC_EINVAL, "unknown depth_type");
+  if (n_ctgs && (!d_seq_offsets || !d_depths || (n_bases && !d_seqs))) return h->fail(MHMKC_EINVAL, "null device buffer");
+  return h->add_ctgs_dev(d_seqs, d_seq_offsets, d_depths, depth_type, n_ctgs, n_bases);
+}
+
+static int uutigs_need(mhmkc_t h);
+
+int mhmkc_add_ctgs_from(mhmkc_t h, mhmkc_t src) {
+  if (!h) return MHMKC_EINVAL;
+  if (!src) return h->fail(MHMKC_EINVAL, "null source handle");
+  if (h->cfg.n_ranks > 1) return h->fail(MHMKC_EUNSUPPORTED, "device contigs: single-rank handles only");
+  if (h->finished) return h->fail(MHMKC_ESTATE, "handle already finished; call mhmkc_reset first");
+  if (src->dev != h->dev) return h->fail(MHMKC_EINVAL, "the handles are on different devices");
+  int rc = uutigs_need(src);  // built now if the finished source has none yet; its own multi-rank / state errors
+  if (rc) return h->fail(rc, "source handle: %s", src->err.c_str());
+  if (src->stream != h->stream) {  // the source's stream before ours, by an event
+    hipEvent_t ev = h->take_event();
+    hipError_t e = hipEventRecord(ev, src->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ev, 0);
+    h->ev_pool.push_back(ev);
+    if (e != hipSuccess) return h->hip_fail(e, "add_ctgs_from");
+  }
+  return h->add_ctgs_dev(src->d_useq.as<char>(), src->u_offsets(), src->u_depths(), MHMKC_DEPTH_F64, src->u_nctgs,
+                         src->u_nbases);
 }
 
 int mhmkc_set_dmin_thres(mhmkc_t h, int32_t dmin_thres) {
@@ -4373,6 +4557,8 @@ int mhmkc_reset(mhmkc_t h) {
   h->ctg_win.assign(1, 0);
   h->ctg_depth.clear();
   h->ctg_n = 0;
+  const bool had_pc = h->pc_on;
+  h->pc_drop();
   h->fq_reads = h->fq_bases = 0;
   h->finished = false;
   h->began = false;
@@ -4382,7 +4568,7 @@ int mhmkc_reset(mhmkc_t h) {
   const bool had_query = h->d_qidx.p || h->d_links.p || h->d_qstage.p || h->d_uctg.p || h->d_urows.p || h->d_useq.p;
   h->drop_query();
   memset(&h->st, 0, sizeof h->st);
-  if (had_query) {  // (the query buffers were counted into the finished round's device_bytes: report what is left)
+  if (had_query || had_pc) {  // (these buffers were counted into the finished round's device_bytes: report what is left)
     h->st.device_bytes = g_dev_live.load();
     h->st.device_bytes_peak = g_dev_peak.load();
   }
@@ -4422,6 +4608,7 @@ int mhmkc_debug_set(const char *knob, int64_t value) {
   else if (k == "query_slots_log2") g_dbg.query_slots_log2 = value;
   else if (k == "query_grid") mhm::query_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else if (k == "merge_grid") mhm::merge_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
+  else if (k == "ctg_pack_grid") mhm::ctg_pack_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else return MHMKC_EINVAL;
   return MHMKC_OK;
 }
@@ -4430,6 +4617,7 @@ void mhmkc_debug_reset(void) {
   g_dbg = DebugKnobs();
   mhm::query_grid_cap = 0;
   mhm::merge_grid_cap = 0;
+  mhm::ctg_pack_grid_cap = 0;
 }
 
 int mhmkc_debug_nib_pack(const uint8_t *src, uint64_t n, uint8_t *dst, int qcut, int mode) {

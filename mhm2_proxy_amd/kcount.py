@@ -381,6 +381,43 @@ class KmerCounter:
         blob = "".join(seqs).encode("ascii")
         self._check(N.lib().mhmkc_add_ctgs(self._h, blob, offs.ctypes.data, d.ctypes.data, len(seqs)))
 
+    def add_ctgs_tensors(self, seqs_t, offsets_t, depths_t, n_bases: int | None = None) -> None:
+        """add_ctgs with device-resident torch tensors (mhmkc_add_ctgs_device): uint8 ASCII bases back to back,
+        int64/uint64 offsets with n_ctgs + 1 entries, one depth per contig as float64 (a Contig::depth, converted as
+        Contig::get_uint16_t_depth() does) or uint16. The tensors are read during the call only. n_bases defaults
+        to the bases tensor's size; the library checks it against offsets_t[-1] on the device."""
+        import torch
+
+        n_ctgs = int(offsets_t.numel()) - 1
+        if n_ctgs < 0:
+            raise ValueError("offsets needs n_ctgs + 1 entries")
+        if int(depths_t.numel()) != n_ctgs:
+            raise ValueError("one depth per contig")
+        if seqs_t.dtype != torch.uint8 or offsets_t.dtype not in (torch.int64, torch.uint64):
+            raise TypeError("seqs_t must be uint8, offsets_t int64 or uint64")
+        if depths_t.dtype == torch.float64:
+            kind = N.MHMKC_DEPTH_F64
+        elif depths_t.dtype == torch.uint16:
+            kind = N.MHMKC_DEPTH_U16
+        else:
+            raise TypeError("depths_t must be float64 or uint16")
+        for t in (seqs_t, offsets_t, depths_t):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("contiguous device tensors expected")
+        if n_bases is None:
+            n_bases = int(seqs_t.numel())
+        if n_bases > int(seqs_t.numel()):
+            raise ValueError("n_bases exceeds the bases tensor")
+        self._after_torch(seqs_t)
+        self._check(N.lib().mhmkc_add_ctgs_device(self._h, seqs_t.data_ptr(), offsets_t.data_ptr(), depths_t.data_ptr(),
+                                                  kind, n_ctgs, n_bases))
+
+    def add_ctgs_from(self, other: "KmerCounter") -> None:
+        """The uutigs of a finished counter as this round's contigs, handed over on the device (mhmkc_add_ctgs_from):
+        the step from one contigging round to the next k (src/contigging.cpp:93-158). The uutigs are built first if
+        `other` has none yet."""
+        self._check(N.lib().mhmkc_add_ctgs_from(self._h, other._h))
+
     # -- ranks, thresholds
     def set_transport(self, transport: "TorchDistTransport") -> None:
         """Host-staged exchange between ranks (mhmkc_set_transport), e.g. over a gloo process group."""
