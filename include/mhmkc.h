@@ -23,7 +23,8 @@
  *     GPU, all ranks calling the same sequence; the k-mer exchange is an all-to-all inside mhmkc_finish
  *     (replacing the UPC++ supermer store, src/kcount/kmer_dht.cpp:133-149,222-224): RCCL over xGMI
  *     (mhmkc_config.comm_id), or a host-staged transport the caller provides (mhmkc_set_transport: a
- *     UPC++/MPI/gloo host, several nodes, or several ranks sharing one GPU).
+ *     UPC++/MPI/gloo host, several nodes, or several ranks sharing one GPU). The traversal of a contigging round
+ *     over all ranks' tables is mhmkc_uutigs_ranks, collective over the same transport.
  */
 #ifndef MHMKC_H
 #define MHMKC_H
@@ -276,7 +277,8 @@ int mhmkc_add_ctgs_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_o
  * mhmkc_uutigs_device(src) with MHMKC_DEPTH_F64 (the step from one contigging round to the next k,
  * src/contigging.cpp:93-158; k may differ between the handles). The uutigs are built first if src has none yet; src's
  * stream is ordered before h's by an event. src not finished: MHMKC_ESTATE; another device: MHMKC_EINVAL; src with
- * n_ranks > 1: mhmkc_uutigs's MHMKC_EUNSUPPORTED. The failure's text is in mhmkc_last_error(h). */
+ * n_ranks > 1 and no mhmkc_uutigs_ranks build: mhmkc_uutigs's MHMKC_EUNSUPPORTED. The failure's text is in
+ * mhmkc_last_error(h). */
 int mhmkc_add_ctgs_from(mhmkc_t h, mhmkc_t src);
 
 /* The depth threshold of the finish: the reference's global _dmin_thres (src/kcount/kmer_dht.hpp:57), which
@@ -401,7 +403,9 @@ int mhmkc_dbjg_links_device(mhmkc_t h, const uint32_t **d_next, const uint8_t **
  * Built once per finish (the index and the links first if needed), kept until the next reset / finish / destroy and
  * counted in mhmkc_stats.device_bytes[_peak]: 9 bytes per row (the row map), 1 per base, 20 per contig + 8. The
  * ranking's scratch (128 bytes per row at its peak) is freed before the call returns. Single-rank handles only
- * (MHMKC_EUNSUPPORTED with n_ranks > 1, checked before the state); before finish: MHMKC_ESTATE; at most 2^32-2 rows. */
+ * (MHMKC_EUNSUPPORTED with n_ranks > 1, checked before the state; with several ranks the uutigs are built by
+ * mhmkc_uutigs_ranks, after which this call and the getters below answer for this rank's part); before finish:
+ * MHMKC_ESTATE; at most 2^32-2 rows. */
 int mhmkc_uutigs(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases);
 /* Host copies (any may be NULL): offsets[n_ctgs + 1] into seqs[n_bases] (ASCII ACGT, the format mhmkc_add_ctgs takes),
  * depths[n_ctgs], n_kmers[n_ctgs] (m). */
@@ -428,6 +432,48 @@ typedef struct {
   double ms_round[MHMKC_UUTIG_MAX_ROUNDS]; /* the first rounds' times, one by one */
 } mhmkc_uutig_info;
 int mhmkc_uutigs_info(mhmkc_t h, mhmkc_uutig_info *info);
+
+/* The uutigs of the union of all ranks' tables: traverse_debruijn_graph at rank_n() > 1 (src/dbjg_traversal.cpp:291-335,
+ * 517-567,569-596). Collective over the ranks of a finished MHMKC_OWNER_MINIMIZER handle (every rank calls it, a rank
+ * without rows too). The result does not depend on the number of ranks:
+ *   a contig is what mhmkc_uutigs gives for the union table at one rank (component, start, strand, layout, n_kmers,
+ *   depth bits: the rule above, the even-k strand note included);
+ *   it belongs to the rank that holds its start row; a rank's contigs are ordered by start key; a contig's global id is
+ *   first_id (the number of contigs of the lower ranks, reduce_prefix of dbjg_traversal.cpp:581-587) + its local index.
+ *   So the ranks' lists, concatenated and sorted by start key, are the single-rank list.
+ * How: the replicated build. Every rank receives the other ranks' rows over the handle's transport
+ * (RCCL or mhmkc_set_transport), ranks the union on its GPU with mhmkc_uutigs's kernels and keeps its own contigs and the
+ * row map of its own rows; the union, its index and links are freed before the call returns. The union has at most
+ * 2^32-2 rows (MHMKC_EUNSUPPORTED beyond, on every rank).
+ * After a successful call mhmkc_uutigs, mhmkc_uutigs_fetch, mhmkc_uutigs_device, mhmkc_uutig_rows[_device] and
+ * mhmkc_uutigs_info answer on this handle for this rank: its contigs, and for every one of its rows row_ctg (the GLOBAL
+ * contig id, also when the contig belongs to another rank; MHMKC_NO_ROW: in no contig), row_pos and row_rc. Kept until
+ * the next reset / finish / destroy and counted in mhmkc_stats.device_bytes[_peak]. Without such a build every call that
+ * is MHMKC_EUNSUPPORTED on a multi-rank handle stays so.
+ * n_ranks == 1: mhmkc_uutigs with *first_id = 0 (whatever the owner). n_ranks > 1 with MHMKC_OWNER_HASH:
+ * MHMKC_EUNSUPPORTED (the reference's own placement is the supported one); before finish: MHMKC_ESTATE; both before any
+ * collective. A failure on any rank after the first collective is a failure on every rank (the ranks exchange their
+ * status at the end): MHMKC_ETRANSPORT on the ranks that did not fail themselves. Any output pointer may be NULL. */
+int mhmkc_uutigs_ranks(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases, uint64_t *first_id, uint64_t *n_ctgs_all);
+
+/* How the last mhmkc_uutigs_ranks went. Stages: rows moved between the ranks, the ranking of the union, the selection
+ * of this rank's part. Routed records are table rows; only MHMKC_URANKS_GATHER moves any. */
+enum { MHMKC_URANKS_GATHER = 0, MHMKC_URANKS_BUILD = 1, MHMKC_URANKS_SELECT = 2, MHMKC_URANKS_STAGES = 3 };
+typedef struct {
+  uint64_t n_ctgs, n_bases;      /* this rank's */
+  uint64_t first_id, n_ctgs_all;
+  uint64_t n_rows, n_rows_all;   /* this rank's rows, the union's */
+  uint64_t rounds;               /* pointer-jumping rounds over all ports of the union */
+  uint64_t cycle_rounds;         /* rounds over the ports on cycles alone */
+  uint64_t cycle_ports;          /* ports left on cycles (two per cycle row of the union) */
+  uint64_t routed_records_sent[MHMKC_URANKS_STAGES], routed_records_recv[MHMKC_URANKS_STAGES];
+  uint64_t routed_bytes_sent[MHMKC_URANKS_STAGES], routed_bytes_recv[MHMKC_URANKS_STAGES];
+  double ms_stage[MHMKC_URANKS_STAGES]; /* device events on the handle's stream (the gather includes its host staging) */
+  double ms_total;
+  uint64_t scratch_bytes;        /* the peak of the build's device memory above what stays */
+  uint64_t kept_bytes;           /* what stays: this rank's contig arrays and row map */
+} mhmkc_uutig_ranks_info;
+int mhmkc_uutigs_ranks_info(mhmkc_t h, mhmkc_uutig_ranks_info *info);
 
 /* Host-staged exchange between ranks (instead of RCCL): for n_ranks > 1 with comm_id == NULL, set before
  * the first mhmkc_finish. Every rank's callbacks are called collectively, in the same order on all ranks, with

@@ -51,11 +51,12 @@ ABI_SYMBOLS = [
     "mhmkc_wait_stream", "mhmkc_set_dmin_thres", "mhmkc_set_transport", "mhmkc_minimizer_hashes",
     "mhmkc_lookup", "mhmkc_lookup_device", "mhmkc_dbjg_links", "mhmkc_dbjg_links_device",
     "mhmkc_uutigs", "mhmkc_uutigs_fetch", "mhmkc_uutigs_device", "mhmkc_uutig_rows", "mhmkc_uutig_rows_device",
-    "mhmkc_uutigs_info",
+    "mhmkc_uutigs_info", "mhmkc_uutigs_ranks", "mhmkc_uutigs_ranks_info",
     "mhmkc_add_ctgs_device", "mhmkc_add_ctgs_from",
 ]
 MHMKC_DEPTH_U16, MHMKC_DEPTH_F64 = 0, 1
 UUTIG_MAX_ROUNDS = 48
+URANKS_STAGES = ("gather", "build", "select")  # MHMKC_URANKS_*
 SYNTH_SYMBOLS = ["mhmkc_synth_config_init", "mhmkc_synth_genome", "mhmkc_synth_reads"]
 # the test-only entry point (include/mhmkc_debug.h)
 DEBUG_SYMBOLS = ["mhmkc_debug_examine4", "mhmkc_debug_nib_pack", "mhmkc_debug_reset", "mhmkc_debug_set"]
@@ -71,6 +72,22 @@ class MhmkcUutigInfo(C.Structure):
     def as_dict(self) -> dict:
         d = {f: getattr(self, f) for f, _ in self._fields_ if f != "ms_round"}
         d["ms_round"] = list(self.ms_round)[:min(int(self.rounds), UUTIG_MAX_ROUNDS)]
+        return d
+
+
+class MhmkcUutigRanksInfo(C.Structure):
+    """mhmkc_uutig_ranks_info (include/mhmkc.h)."""
+    _PER_STAGE = ("routed_records_sent", "routed_records_recv", "routed_bytes_sent", "routed_bytes_recv")
+    _fields_ = [(f, C.c_uint64) for f in ("n_ctgs", "n_bases", "first_id", "n_ctgs_all", "n_rows", "n_rows_all", "rounds",
+                                          "cycle_rounds", "cycle_ports")] + \
+               [(f, C.c_uint64 * len(URANKS_STAGES)) for f in _PER_STAGE] + \
+               [("ms_stage", C.c_double * len(URANKS_STAGES)), ("ms_total", C.c_double),
+                ("scratch_bytes", C.c_uint64), ("kept_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, t in self._fields_ if t in (C.c_uint64, C.c_double)}
+        for f in self._PER_STAGE + ("ms_stage",):
+            d[f] = dict(zip(URANKS_STAGES, list(getattr(self, f))))
         return d
 
 
@@ -277,6 +294,8 @@ def lib() -> C.CDLL:
     L.mhmkc_uutig_rows.argtypes = [VP, VP, VP, VP]
     L.mhmkc_uutig_rows_device.argtypes = [VP, P(VP), P(VP), P(VP)]
     L.mhmkc_uutigs_info.argtypes = [VP, P(MhmkcUutigInfo)]
+    L.mhmkc_uutigs_ranks.argtypes = [VP, P(U64), P(U64), P(U64), P(U64)]
+    L.mhmkc_uutigs_ranks_info.argtypes = [VP, P(MhmkcUutigRanksInfo)]
     _lib = L
     return L
 

@@ -509,4 +509,27 @@ hipError_t launch_uutig_bases(const OutRows &t, uint64_t n, int k, int nl, int n
                               const uint32_t *row_pos, const uint8_t *row_rc, const uint64_t *offsets,
                               const uint32_t *n_kmers, uint64_t n_ctgs, uint64_t n_bases, char *seqs, hipStream_t s);
 
+// What a rank keeps of the uutigs of the union of all ranks' tables (kcount_uutig_ranks.hip). The
+// union's rows lie in rank order, rank r's at [base[r], base[r + 1]) (base: g + 1 device words); starts: the union's start
+// rows in contig order. One scratch buffer of uutig_ranks_scratch_bytes serves _ids and _take, which hand out pointers
+// into it.
+size_t uutig_ranks_scratch_bytes(uint64_t n_ctgs);
+// order: the union's contigs sorted (stably) by the rank of their start row; gid[c]: contig c's place in it, its global
+// id; first[r] (g + 1 device words): the first place of rank r, ~0 when it has no contig
+hipError_t launch_uutig_ranks_ids(const uint32_t *starts, uint64_t n_ctgs, const uint64_t *base, int g, void *scratch,
+                                  size_t scratch_bytes, const uint32_t **order, const uint32_t **gid, uint64_t *first,
+                                  hipStream_t s);
+// places [first_me, first_me + n_mine) of order: n_kmers / depths [n_mine], offsets [n_mine + 1]
+hipError_t launch_uutig_ranks_take(const uint32_t *order, uint64_t first_me, uint64_t n_mine, uint64_t n_ctgs,
+                                   const uint64_t *uoff, const double *udepths, const uint32_t *unk, void *scratch,
+                                   size_t scratch_bytes, uint32_t *n_kmers, double *depths, uint64_t *offsets,
+                                   hipStream_t s);
+hipError_t launch_uutig_ranks_seqs(const uint32_t *order, uint64_t first_me, uint64_t n_mine, uint64_t n_ctgs,
+                                   const uint64_t *uoff, const char *useq, uint64_t u_bases, const uint64_t *offsets,
+                                   uint64_t n_bases, char *seqs, hipStream_t s);
+// the row map of union rows [base_me, base_me + n_me) with global contig ids
+hipError_t launch_uutig_ranks_rows(const uint32_t *urow_ctg, const uint32_t *urow_pos, const uint8_t *urow_rc,
+                                   uint64_t n_rows, uint64_t base_me, uint64_t n_me, const uint32_t *gid, uint64_t n_ctgs,
+                                   uint32_t *row_ctg, uint32_t *row_pos, uint8_t *row_rc, hipStream_t s);
+
 }  // namespace mhm

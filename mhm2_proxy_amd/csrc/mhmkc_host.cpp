@@ -506,7 +506,26 @@ struct mhmkc {
   const uint64_t *u_offsets() const { return d_uctg.as<uint64_t>(); }
   const double *u_depths() const { return (const double *)(d_uctg.as<char>() + align_up((u_nctgs + 1) * 8, 256)); }
   const uint32_t *u_nkmers() const { return (const uint32_t *)((const char *)u_depths() + align_up(u_nctgs * 8 + 8, 256)); }
+  // the uutigs of all ranks' tables (mhmkc_uutigs_ranks, kcount_uutig_ranks.hip): d_un holds the union
+  // table (keys, counts, left, right) while it is ranked in the place of the rank's own, d_ustarts the union's sorted
+  // start rows (uutigs_build leaves them there when u_keep_starts is set), d_ursel the selection's scratch, d_urk the rank
+  // bases and first places. All scratch: what stays is this rank's part in d_uctg / d_useq / d_urows, as for one rank.
+  DevBuf d_un[4], d_ustarts, d_ursel, d_urk;
+  bool u_keep_starts = false, uranks_ready = false;
+  uint64_t ur_first = 0, ur_all = 0;
+  mhmkc_uutig_ranks_info urinfo{};
+  int uutigs_ranks();
+  int uutigs_ranks_build(std::vector<hipEvent_t> &evs);
+  void drop_uranks_scratch() {
+    for (DevBuf &b : d_un) b.release();
+    d_ustarts.release();
+    d_ursel.release();
+    d_urk.release();
+  }
   void drop_query() {
+    drop_uranks_scratch();
+    uranks_ready = false;
+    ur_first = ur_all = 0;
     d_qidx.release();
     d_links.release();
     d_qstage.release();
@@ -4416,6 +4435,10 @@ int mhmkc::uutigs_build(std::vector<hipEvent_t> &evs) {
                                    d_useq.as<char>(), stream)) != hipSuccess)
     return hip_fail(e, "uutig rows");
   const int t5 = mark();
+  if (u_keep_starts && n_ctgs &&  // (mhmkc_uutigs_ranks: the sorted starts name every contig's owner)
+      ((e = grow(d_ustarts, n_ctgs * 4 + 64)) != hipSuccess ||
+       (e = hipMemcpyAsync(d_ustarts.p, starts, n_ctgs * 4, hipMemcpyDeviceToDevice, stream)) != hipSuccess))
+    return hip_fail(e, "uutig starts");
   if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(e, "uutigs");
   uinfo.n_ctgs = n_ctgs;
   uinfo.n_bases = n_bases;
@@ -4453,9 +4476,237 @@ int mhmkc::uutigs() {
   return rc;
 }
 
+// The uutigs of the union of all ranks' tables, the replicated build (traverse_debruijn_graph at rank_n() > 1,
+// src/dbjg_traversal.cpp:291-335,517-567,569-596). Collectives, in this order on every rank: the row
+// counts, the allocation verdicts, the rows, the status. Between the rows and the status a rank works alone, so a
+// failure there reaches the status exchange and every rank returns an error.
+int mhmkc::uutigs_ranks_build(std::vector<hipEvent_t> &evs) {
+  const int g = G(), me = cfg.rank;
+  hipError_t e = hipSuccess;
+  int rc;
+  auto mark = [&]() -> int {
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return -1;
+    (void)hipEventRecord(ev, stream);
+    evs.push_back(ev);
+    return (int)evs.size() - 1;
+  };
+  auto ms = [&](int a, int b) -> double {
+    float f = 0;
+    if (a < 0 || b < 0 || hipEventElapsedTime(&f, evs[(size_t)a], evs[(size_t)b]) != hipSuccess) return 0;
+    return (double)f;
+  };
+  // the fixed buffer, before the first collective: the rank bases and the ranks' first places
+  if ((e = grow(d_urk, 16 * (size_t)(g + 1) + 64)) != hipSuccess)
+    return e == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "uutigs_ranks: rank table") : hip_fail(e, "uutigs_ranks");
+  uint64_t *d_base = d_urk.as<uint64_t>(), *d_first = d_base + (g + 1);
+
+  // 1. the union table: every rank's rows, in rank order
+  const uint64_t n_me = n_out;
+  std::vector<uint64_t> ns((size_t)g, 0), base((size_t)g + 1, 0), first((size_t)g + 1, 0);
+  if ((rc = allgather_host(&n_me, ns.data(), 8))) return rc;
+  for (int r = 0; r < g; r++) base[(size_t)r + 1] = base[(size_t)r] + ns[(size_t)r];
+  const uint64_t N = base[(size_t)g];
+  if (ns[(size_t)me] != n_me) return fail(MHMKC_ETRANSPORT, "uutigs_ranks: the gathered row counts do not hold this rank's");
+  if (N >= 0xffffffffull)  // (every rank sees the same N)
+    return fail(MHMKC_EUNSUPPORTED, "uutigs_ranks: the union has %llu rows, at most 2^32-2", (unsigned long long)N);
+  urinfo.n_rows = n_me;
+  urinfo.n_rows_all = N;
+  const int t0 = mark();
+  const size_t kb = 8 * (size_t)nlo;
+  DevBuf *outs[4] = {&d_out_keys, &d_out_counts, &d_out_left, &d_out_right};
+  const size_t rowb[4] = {kb, 2, 1, 1};
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(e, "uutigs_ranks");
+  for (int i = 0; i < 4 && e == hipSuccess; i++) e = d_un[i].ensure(N * rowb[i] + 64);
+  if (e != hipSuccess) (void)hipGetLastError();
+  const uint64_t ok = e == hipSuccess ? 1 : 0;
+  std::vector<uint64_t> oks((size_t)g, 0);
+  if ((rc = allgather_host(&ok, oks.data(), 8))) return rc;
+  for (int r = 0; r < g; r++)
+    if (!oks[(size_t)r])
+      return fail(MHMKC_ENOMEM, "uutigs_ranks: rank %d could not allocate the union table of %llu rows", r,
+                  (unsigned long long)N);
+  std::vector<Xfer> snd, rcv;
+  for (int i = 0; i < 4 && n_me; i++)
+    if ((e = hipMemcpyAsync(d_un[i].as<char>() + base[(size_t)me] * rowb[i], outs[i]->p, n_me * rowb[i],
+                            hipMemcpyDeviceToDevice, stream)) != hipSuccess)
+      return hip_fail(e, "uutigs_ranks: own rows");
+  for (int p = 0; p < g; p++) {
+    if (p == me) continue;
+    for (int i = 0; i < 4; i++) {
+      if (n_me) snd.push_back({p, outs[i]->p, n_me * rowb[i]});
+      if (ns[(size_t)p]) rcv.push_back({p, d_un[i].as<char>() + base[(size_t)p] * rowb[i], ns[(size_t)p] * rowb[i]});
+    }
+  }
+  const uint64_t sent0 = st.bytes_sent, recv0 = st.bytes_recv;
+  rc = move(snd, rcv);
+  st.bytes_sent = sent0;  // bytes_* count the record exchange only
+  st.bytes_recv = recv0;
+  if (rc) return rc;
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(e, "uutigs_ranks: rows");
+  urinfo.routed_records_sent[MHMKC_URANKS_GATHER] = n_me * (uint64_t)(g - 1);
+  urinfo.routed_bytes_sent[MHMKC_URANKS_GATHER] = n_me * (uint64_t)(g - 1) * (kb + 4);
+  urinfo.routed_records_recv[MHMKC_URANKS_GATHER] = N - n_me;
+  urinfo.routed_bytes_recv[MHMKC_URANKS_GATHER] = (N - n_me) * (kb + 4);
+  const int t1 = mark();
+  int t2 = -1, t3 = -1;
+  uint64_t union_bytes = 0;
+
+  // 2. and 3., on this rank alone: the union ranked in the place of the rank's own table, then the rank's part of it
+  DevBuf nctg, nseq, nrows;
+  auto local = [&]() -> int {
+    for (int i = 0; i < 4; i++) std::swap(*outs[i], d_un[i]);
+    n_out = N;
+    u_keep_starts = true;
+    int r = uutigs();
+    u_keep_starts = false;
+    for (int i = 0; i < 4; i++) std::swap(*outs[i], d_un[i]);
+    n_out = n_me;
+    union_bytes = d_qidx.cap + d_links.cap;
+    d_qidx.release();  // the union's index and links are not this rank's
+    d_links.release();
+    qidx = mhm::QueryIndex{};
+    qidx_ready = links_ready = uutigs_ready = false;
+    if (r) return r;
+    t2 = mark();
+    const uint64_t NC = u_nctgs, NB = u_nbases;
+    const size_t sb = mhm::uutig_ranks_scratch_bytes(NC);
+    hipError_t e2;
+    if ((e2 = grow(d_ursel, sb)) != hipSuccess) return hip_fail(e2, "uutigs_ranks: selection scratch");
+    const uint32_t *order = nullptr, *gid = nullptr;
+    if ((e2 = hipMemcpyAsync(d_base, base.data(), 8 * (size_t)(g + 1), hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e2 = mhm::launch_uutig_ranks_ids(d_ustarts.as<uint32_t>(), NC, d_base, g, d_ursel.p, sb, &order, &gid, d_first,
+                                          stream)) != hipSuccess ||
+        (e2 = hipMemcpyAsync(first.data(), d_first, 8 * (size_t)(g + 1), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e2 = hipStreamSynchronize(stream)) != hipSuccess)
+      return hip_fail(e2, "uutigs_ranks: contig owners");
+    if (first[(size_t)g] != ~0ull) return fail(MHMKC_EHIP, "uutigs_ranks: a contig's start lies outside the union");
+    uint64_t nxt = NC;
+    for (int r2 = g - 1; r2 >= 0; r2--) {  // a rank without contigs starts where the next one does
+      if (first[(size_t)r2] == ~0ull) first[(size_t)r2] = nxt;
+      if (first[(size_t)r2] > nxt) return fail(MHMKC_EHIP, "uutigs_ranks: the ranks' contigs are not in rank order");
+      nxt = first[(size_t)r2];
+    }
+    first[(size_t)g] = NC;
+    if (nxt != 0) return fail(MHMKC_EHIP, "uutigs_ranks: the ranks' contigs do not start at 0");
+    const uint64_t f_me = first[(size_t)me], n_mine = first[(size_t)me + 1] - f_me;
+    const size_t off_b = align_up((n_mine + 1) * 8, 256), dep_b = align_up(n_mine * 8 + 8, 256);
+    if ((e2 = nctg.ensure(off_b + dep_b + n_mine * 4 + 64)) != hipSuccess)
+      return e2 == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "uutigs_ranks: %llu contigs", (unsigned long long)n_mine)
+                                       : hip_fail(e2, "uutigs_ranks: contig table");
+    uint64_t *offsets = nctg.as<uint64_t>();
+    double *depths = (double *)(nctg.as<char>() + off_b);
+    uint32_t *n_kmers = (uint32_t *)(nctg.as<char>() + off_b + dep_b);
+    uint64_t nb_mine = 0;
+    if ((e2 = mhm::launch_uutig_ranks_take(order, f_me, n_mine, NC, u_offsets(), u_depths(), u_nkmers(), d_ursel.p, sb,
+                                           n_kmers, depths, offsets, stream)) != hipSuccess ||
+        (e2 = hipMemcpyAsync(&nb_mine, offsets + n_mine, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e2 = hipStreamSynchronize(stream)) != hipSuccess)
+      return hip_fail(e2, "uutigs_ranks: contig table");
+    if (nb_mine > NB) return fail(MHMKC_EHIP, "uutigs_ranks: %llu bases of the union's %llu", (unsigned long long)nb_mine,
+                                  (unsigned long long)NB);
+    const size_t rows_b = align_up(n_me * 4, 256), urows_b = align_up(N * 4, 256);
+    if ((nb_mine && (e2 = nseq.ensure(nb_mine)) != hipSuccess) ||
+        (n_me && (e2 = nrows.ensure(2 * rows_b + n_me + 64)) != hipSuccess))
+      return e2 == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "uutigs_ranks: %llu bases", (unsigned long long)nb_mine)
+                                       : hip_fail(e2, "uutigs_ranks: bases");
+    const char *ur = d_urows.as<char>();
+    if ((e2 = mhm::launch_uutig_ranks_seqs(order, f_me, n_mine, NC, u_offsets(), d_useq.as<char>(), NB, offsets, nb_mine,
+                                           nseq.as<char>(), stream)) != hipSuccess ||
+        (e2 = mhm::launch_uutig_ranks_rows((const uint32_t *)ur, (const uint32_t *)(ur + urows_b),
+                                           (const uint8_t *)(ur + 2 * urows_b), N, base[(size_t)me], n_me, gid, NC,
+                                           nrows.as<uint32_t>(), (uint32_t *)(nrows.as<char>() + rows_b),
+                                           (uint8_t *)(nrows.as<char>() + 2 * rows_b), stream)) != hipSuccess)
+      return hip_fail(e2, "uutigs_ranks: rows");
+    t3 = mark();
+    if ((e2 = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(e2, "uutigs_ranks");
+    union_bytes += d_uctg.cap + d_useq.cap + d_urows.cap;
+    d_uctg.release();  // the union's contigs and row map give way to this rank's
+    d_useq.release();
+    d_urows.release();
+    d_uctg = nctg;
+    d_useq = nseq;
+    d_urows = nrows;
+    nctg = nseq = nrows = DevBuf{};
+    u_nctgs = n_mine;
+    u_nbases = nb_mine;
+    ur_first = f_me;
+    ur_all = NC;
+    return MHMKC_OK;
+  };
+  const int lrc = local();
+  if (lrc) {
+    (void)hipStreamSynchronize(stream);
+    nctg.release();
+    nseq.release();
+    nrows.release();
+  }
+
+  // 4. the status: a rank that failed alone fails every rank, and the ranks agree on who has how many contigs
+  const uint64_t mine[2] = {(uint64_t)(lrc ? 1 : 0), lrc ? 0 : u_nctgs};
+  std::vector<uint64_t> all(2 * (size_t)g, 0);
+  const std::string lerr = err;
+  if ((rc = allgather_host(mine, all.data(), 16))) return rc;
+  if (lrc) {
+    err = lerr;
+    return lrc;
+  }
+  for (int r = 0; r < g; r++) {
+    if (all[2 * (size_t)r])
+      return fail(MHMKC_ETRANSPORT, "uutigs_ranks: rank %d failed (its mhmkc_last_error says why)", r);
+    if (all[2 * (size_t)r + 1] != first[(size_t)r + 1] - first[(size_t)r])
+      return fail(MHMKC_ETRANSPORT, "uutigs_ranks: rank %d keeps %llu contigs where this rank expects it to keep %llu", r,
+                  (unsigned long long)all[2 * (size_t)r + 1],
+                  (unsigned long long)(first[(size_t)r + 1] - first[(size_t)r]));
+  }
+  urinfo.n_ctgs = u_nctgs;
+  urinfo.n_bases = u_nbases;
+  urinfo.first_id = ur_first;
+  urinfo.n_ctgs_all = ur_all;
+  urinfo.rounds = uinfo.rounds;
+  urinfo.cycle_rounds = uinfo.cycle_rounds;
+  urinfo.cycle_ports = uinfo.cycle_ports;
+  urinfo.ms_stage[MHMKC_URANKS_GATHER] = ms(t0, t1);
+  urinfo.ms_stage[MHMKC_URANKS_BUILD] = ms(t1, t2);
+  urinfo.ms_stage[MHMKC_URANKS_SELECT] = ms(t2, t3);
+  urinfo.ms_total = ms(t0, t3);
+  urinfo.kept_bytes = d_uctg.cap + d_useq.cap + d_urows.cap;
+  urinfo.scratch_bytes = uinfo.scratch_bytes + union_bytes + d_un[0].cap + d_un[1].cap + d_un[2].cap + d_un[3].cap +
+                         d_ustarts.cap + d_ursel.cap + d_urk.cap;
+  // mhmkc_uutigs_info then speaks of this rank's part too
+  uinfo.n_ctgs = u_nctgs;
+  uinfo.n_bases = u_nbases;
+  uinfo.kept_bytes = urinfo.kept_bytes;
+  uinfo.scratch_bytes = urinfo.scratch_bytes;
+  return MHMKC_OK;
+}
+
+int mhmkc::uutigs_ranks() {
+  if (uranks_ready) return MHMKC_OK;
+  drop_query();  // this rank's own index, links and uutigs make room for the union's
+  urinfo = mhmkc_uutig_ranks_info{};
+  std::vector<hipEvent_t> evs;
+  const int rc = uutigs_ranks_build(evs);
+  if (rc) (void)hipStreamSynchronize(stream);
+  for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+  drop_uranks_scratch();
+  if (rc) {
+    d_uctg.release();
+    d_useq.release();
+    d_urows.release();
+    u_nctgs = u_nbases = ur_first = ur_all = 0;
+    uutigs_ready = false;
+  } else {
+    uutigs_ready = uranks_ready = true;
+  }
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return rc;
+}
+
 static int uutigs_need(mhmkc_t h) {
   if (!h) return MHMKC_EINVAL;
-  if (h->cfg.n_ranks > 1) return h->fail(MHMKC_EUNSUPPORTED, "uutigs: single-rank handles only");
+  if (h->cfg.n_ranks > 1 && !h->uranks_ready) return h->fail(MHMKC_EUNSUPPORTED, "uutigs: single-rank handles only");
   if (!h->finished) return h->fail(MHMKC_ESTATE, "uutigs before finish");
   return h->uutigs();
 }
@@ -4523,6 +4774,43 @@ int mhmkc_uutig_rows(mhmkc_t h, uint32_t *row_ctg, uint32_t *row_pos, uint8_t *r
 int mhmkc_uutigs_info(mhmkc_t h, mhmkc_uutig_info *info) {
   if (!h || !info) return MHMKC_EINVAL;
   *info = h->uinfo;
+  return MHMKC_OK;
+}
+
+int mhmkc_uutigs_ranks(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases, uint64_t *first_id, uint64_t *n_ctgs_all) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks <= 1) {  // one rank: mhmkc_uutigs, whose contig ids are the global ones
+    int rc = uutigs_need(h);
+    if (rc) return rc;
+    h->urinfo = mhmkc_uutig_ranks_info{};
+    h->urinfo.n_ctgs = h->urinfo.n_ctgs_all = h->u_nctgs;
+    h->urinfo.n_bases = h->u_nbases;
+    h->urinfo.n_rows = h->urinfo.n_rows_all = h->n_out;
+    h->urinfo.rounds = h->uinfo.rounds;
+    h->urinfo.cycle_rounds = h->uinfo.cycle_rounds;
+    h->urinfo.cycle_ports = h->uinfo.cycle_ports;
+    h->urinfo.ms_stage[MHMKC_URANKS_BUILD] = h->urinfo.ms_total = h->uinfo.ms_links + h->uinfo.ms_total;
+    h->urinfo.scratch_bytes = h->uinfo.scratch_bytes;
+    h->urinfo.kept_bytes = h->uinfo.kept_bytes;
+    h->ur_first = 0;
+    h->ur_all = h->u_nctgs;
+  } else {
+    if (h->cfg.output_owner != MHMKC_OWNER_MINIMIZER)
+      return h->fail(MHMKC_EUNSUPPORTED, "uutigs_ranks: MHMKC_OWNER_MINIMIZER handles only");
+    if (!h->finished) return h->fail(MHMKC_ESTATE, "uutigs_ranks before finish");
+    int rc = h->uutigs_ranks();
+    if (rc) return rc;
+  }
+  if (n_ctgs) *n_ctgs = h->u_nctgs;
+  if (n_bases) *n_bases = h->u_nbases;
+  if (first_id) *first_id = h->ur_first;
+  if (n_ctgs_all) *n_ctgs_all = h->ur_all;
+  return MHMKC_OK;
+}
+
+int mhmkc_uutigs_ranks_info(mhmkc_t h, mhmkc_uutig_ranks_info *info) {
+  if (!h || !info) return MHMKC_EINVAL;
+  *info = h->urinfo;
   return MHMKC_OK;
 }
 

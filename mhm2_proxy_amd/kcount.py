@@ -605,6 +605,24 @@ class KmerCounter:
         self._check(N.lib().mhmkc_uutigs_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    # -- the uutigs of all ranks' tables (mhmkc_uutigs_ranks)
+    def uutigs_ranks(self) -> dict:
+        """Collective over the ranks of a finished MHMKC_OWNER_MINIMIZER counter (mhmkc_uutigs_ranks; traverse_debruijn_graph
+        at rank_n() > 1, src/dbjg_traversal.cpp:291-335,517-567,569-596): the uutigs of the union of all ranks' tables. This
+        rank keeps the contigs whose start row it holds, in start-key order; a contig's global id is first_id + its local
+        index. uutigs(), uutig_rows() (row_ctg: global ids), uutigs_device() and uutig_strings() then give this rank's
+        part. Returns {"n_ctgs", "n_bases", "first_id", "n_ctgs_all"}. One rank: uutigs() with first_id 0."""
+        nc, nb, fi, na = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(N.lib().mhmkc_uutigs_ranks(self._h, C.byref(nc), C.byref(nb), C.byref(fi), C.byref(na)))
+        return {"n_ctgs": int(nc.value), "n_bases": int(nb.value), "first_id": int(fi.value), "n_ctgs_all": int(na.value)}
+
+    def uutigs_ranks_info(self) -> dict:
+        """Rounds, rows and bytes moved between the ranks per stage, stage times (device events) and memory of the last
+        uutigs_ranks build (mhmkc_uutigs_ranks_info)."""
+        info = N.MhmkcUutigRanksInfo()
+        self._check(N.lib().mhmkc_uutigs_ranks_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def stats(self) -> dict:
         s = N.MhmkcStats()
         self._check(N.lib().mhmkc_get_stats(self._h, C.byref(s)))
