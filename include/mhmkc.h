@@ -269,7 +269,17 @@ int mhmkc_add_ctgs(mhmkc_t h, const char *seqs, const uint64_t *seq_offsets, con
  * Contigs are applied in the order they were added, whichever of mhmkc_add_ctgs, mhmkc_add_ctgs_device and
  * mhmkc_add_ctgs_from added them. From the first device add of a round on, the round's contigs are kept on the device
  * (counted in mhmkc_stats.device_bytes[_peak]) until mhmkc_reset or mhmkc_destroy; host adds that follow are uploaded
- * at once. Single-rank handles only (MHMKC_EUNSUPPORTED with n_ranks > 1, checked before the state). */
+ * at once.
+ * Several ranks (n_ranks > 1): accepted with output_owner == MHMKC_OWNER_MINIMIZER, the placement on which
+ * mhmkc_uutigs_ranks produces contigs. The call is local (no collective; the same checks, the same mailbox): every rank
+ * passes its own contigs, possibly none, and the result is the one mhmkc_add_ctgs documents for several ranks: the
+ * contigs of all ranks applied in rank order, within a rank in the order of its calls, the ranks' tables together equal
+ * to a single rank's given the concatenation. Ranks may mix the routes: one may add on the host only, another on the
+ * device only, a third nothing. mhmkc_finish decides from all-gathered values: when no rank of the round holds contigs
+ * on the device, the contigs are gathered through the host as before; otherwise every rank gathers them on the device
+ * (a rank with host contigs uploads them first; DESIGN.md §3.6b, mhmkc_ctgs_ranks_info), and the gathered copy is counted
+ * in device_bytes[_peak] until the finish ends. With MHMKC_OWNER_HASH and n_ranks > 1: MHMKC_EUNSUPPORTED, checked
+ * before the pointers and the state. */
 enum { MHMKC_DEPTH_U16 = 0, MHMKC_DEPTH_F64 = 1 };
 int mhmkc_add_ctgs_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const void *d_depths,
                           int depth_type, uint64_t n_ctgs, uint64_t n_bases);
@@ -277,9 +287,27 @@ int mhmkc_add_ctgs_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_o
  * mhmkc_uutigs_device(src) with MHMKC_DEPTH_F64 (the step from one contigging round to the next k,
  * src/contigging.cpp:93-158; k may differ between the handles). The uutigs are built first if src has none yet; src's
  * stream is ordered before h's by an event. src not finished: MHMKC_ESTATE; another device: MHMKC_EINVAL; src with
- * n_ranks > 1 and no mhmkc_uutigs_ranks build: mhmkc_uutigs's MHMKC_EUNSUPPORTED. The failure's text is in
- * mhmkc_last_error(h). */
+ * n_ranks > 1 and no mhmkc_uutigs_ranks build: mhmkc_uutigs's MHMKC_EUNSUPPORTED; with such a build: this rank's part
+ * of it (possibly no contig), so that every rank calling mhmkc_uutigs_ranks(src) and then mhmkc_add_ctgs_from(h, src)
+ * hands the union's uutigs to the next k. h with n_ranks > 1: as mhmkc_add_ctgs_device (MHMKC_OWNER_MINIMIZER only).
+ * The failure's text is in mhmkc_last_error(h). */
 int mhmkc_add_ctgs_from(mhmkc_t h, mhmkc_t src);
+
+/* How the contigs of the last mhmkc_finish on a handle with n_ranks > 1 reached every rank. All zeros before such a
+ * finish with contigs (and after mhmkc_reset). device_route 0: through the host (no rank held contigs on the device);
+ * the sizes are set, the rest is zero. device_route 1: per peer a rank sends 6 n_ctgs +
+ * ceil(n_bases / 2) bytes (u32 lengths, u16 depths, bases as nibbles). */
+typedef struct {
+  uint64_t device_route;             /* 0 or 1 */
+  uint64_t n_ctgs, n_bases;          /* this rank's contigs and their bases */
+  uint64_t n_ctgs_all, n_bases_all;  /* the round's, over all ranks */
+  uint64_t windows_all;              /* the round's counted contig k-mers (contigs of k + 2 bases or more) */
+  uint64_t bytes_sent, bytes_recv;   /* between the ranks, by this rank */
+  double ms_pack, ms_move, ms_assemble, ms_total; /* device events on the handle's stream (the move includes its host
+                                                     staging under mhmkc_set_transport); ms_total: pack .. assemble */
+  uint64_t gathered_bytes;           /* device memory of the gathered copy (freed when the finish ends) */
+} mhmkc_ctg_ranks_info;
+int mhmkc_ctgs_ranks_info(mhmkc_t h, mhmkc_ctg_ranks_info *info);
 
 /* The depth threshold of the finish: the reference's global _dmin_thres (src/kcount/kmer_dht.hpp:57), which
  * analyze_kmers sets (src/kcount/kcount.cpp:145) after the KmerDHT was built and get_ext reads at finish

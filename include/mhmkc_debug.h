@@ -46,7 +46,10 @@ extern "C" {
  *                 small batch: the prefetched next descriptor, the reuse of the wave's LDS after another pair (0: the
  *                 launches' own grids)
  *   ctg_pack_grid at most v workgroups for k_ctg_pack (kcount_ctgin.hip: mhmkc_add_ctgs_device, mhmkc_add_ctgs_from), so
- *                 that a lane converts several 16-byte vectors in turn on a small batch (0: the launch's own grid) */
+ *                 that a lane converts several 16-byte vectors in turn on a small batch (0: the launch's own grid)
+ *   ctgx_grid     at most v workgroups for the kernels of the multi-rank device gather of contigs (kcount_ctgx.hip:
+ *                 k_ctgx_lens, k_ctgx_pack, k_ctgx_windows), so that their grid-stride loops turn several times on a
+ *                 small set (0: the launches' own grids) */
 int mhmkc_debug_set(const char *knob, int64_t value);
 /* Every knob back to its default. */
 void mhmkc_debug_reset(void);

@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "mhmkc_lookup", "mhmkc_lookup_device", "mhmkc_dbjg_links", "mhmkc_dbjg_links_device",
     "mhmkc_uutigs", "mhmkc_uutigs_fetch", "mhmkc_uutigs_device", "mhmkc_uutig_rows", "mhmkc_uutig_rows_device",
     "mhmkc_uutigs_info", "mhmkc_uutigs_ranks", "mhmkc_uutigs_ranks_info",
-    "mhmkc_add_ctgs_device", "mhmkc_add_ctgs_from",
+    "mhmkc_add_ctgs_device", "mhmkc_add_ctgs_from", "mhmkc_ctgs_ranks_info",
 ]
 MHMKC_DEPTH_U16, MHMKC_DEPTH_F64 = 0, 1
 UUTIG_MAX_ROUNDS = 48
@@ -89,6 +89,17 @@ class MhmkcUutigRanksInfo(C.Structure):
         for f in self._PER_STAGE + ("ms_stage",):
             d[f] = dict(zip(URANKS_STAGES, list(getattr(self, f))))
         return d
+
+
+class MhmkcCtgRanksInfo(C.Structure):
+    """mhmkc_ctg_ranks_info (include/mhmkc.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("device_route", "n_ctgs", "n_bases", "n_ctgs_all", "n_bases_all", "windows_all",
+                                          "bytes_sent", "bytes_recv")] + \
+               [(f, C.c_double) for f in ("ms_pack", "ms_move", "ms_assemble", "ms_total")] + \
+               [("gathered_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class MhmkcConfig(C.Structure):
@@ -296,6 +307,7 @@ def lib() -> C.CDLL:
     L.mhmkc_uutigs_info.argtypes = [VP, P(MhmkcUutigInfo)]
     L.mhmkc_uutigs_ranks.argtypes = [VP, P(U64), P(U64), P(U64), P(U64)]
     L.mhmkc_uutigs_ranks_info.argtypes = [VP, P(MhmkcUutigRanksInfo)]
+    L.mhmkc_ctgs_ranks_info.argtypes = [VP, P(MhmkcCtgRanksInfo)]
     _lib = L
     return L
 

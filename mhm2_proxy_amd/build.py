@@ -29,7 +29,8 @@ LIB = PKG / "libmhmkc.so"
 SYNTH = PKG / "libmhmkc_synth.so"
 ORACLE = ROOT / "oracle" / "liboracle.so"
 
-LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kcount_ctgin.hip", CSRC / "kcount_owner.hip",
+LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kcount_ctgin.hip", CSRC / "kcount_ctgx.hip",
+               CSRC / "kcount_owner.hip",
                CSRC / "kcount_query.hip",
                CSRC / "kcount_uutig.hip", CSRC / "kcount_uutig_ranks.hip",
                CSRC / "fastq.hip",

@@ -228,6 +228,28 @@ hipError_t launch_ctgin(const char *seqs, const uint64_t *offs, const void *dept
                         uint64_t n_bases, int k, uint64_t b0, uint64_t w0, uint8_t *out_bytes, uint64_t *out_offs,
                         uint64_t *out_win, uint16_t *out_depth, void *tmp, size_t tmp_bytes, CtgInBox *box, hipStream_t s);
 
+// The contigs of several ranks gathered on the device (kcount_ctgx.hip). What the kernels find goes to
+// a mailbox the host reads once per gather.
+struct CtgxBox {
+  unsigned long long bad_rank;  // lowest rank whose lengths do not sum to the bytes it announced (~0: none)
+  unsigned long long long_ctg;  // first contig of this rank with 2^32 or more bytes (~0: none)
+  unsigned long long windows;   // the counted windows of the gathered lengths
+};
+// Workgroups of the gather kernels' grid-stride launches. The test knob ctgx_grid (include/mhmkc_debug.h) caps them at
+// ctgx_grid_cap, so that their loops turn several times on a small set; 0, the product's value: their own grids.
+inline unsigned ctgx_grid_cap = 0;
+hipError_t launch_ctgx_begin(CtgxBox *box, hipStream_t s);
+// This rank's wire format: lens[n_ctgs] = offs[i + 1] - offs[i] as u32, nib[(n_bytes + 1) / 2] = the nibbles of
+// bytes[n_bytes] (bytes 16-byte aligned, nib 8-byte aligned: the starts of their buffers).
+hipError_t launch_ctgx_pack(const uint64_t *offs, uint64_t n_ctgs, const uint8_t *bytes, uint64_t n_bytes, uint32_t *lens,
+                            uint8_t *nib, CtgxBox *box, hipStream_t s);
+size_t ctgx_tmp_bytes(uint64_t n_all);
+// lens[n_all], every rank's in rank order -> offs[n_all + 1] (byte offsets), win[n_all + 1] (counted-window prefix);
+// tab[2 (g + 1)] = the ranks' first contigs, then their first bytes, as announced (device memory): the mailbox names a
+// rank whose lengths do not sum to its bytes. No index comes from lens.
+hipError_t launch_ctgx_assemble(const uint32_t *lens, uint64_t n_all, int k, const uint64_t *tab, int g, uint64_t *offs,
+                                uint64_t *win, void *tmp, size_t tmp_bytes, CtgxBox *box, hipStream_t s);
+
 enum {
   STAT_DISTINCT = 0,
   STAT_NOUT = 1,

@@ -420,6 +420,17 @@ MHM_HD uint32_t ctg_pack4(uint32_t x, uint32_t *bad) {
   return code | (upper * 0xF8u);
 }
 
+// Four PackedRead bytes of contigs as four nibbles, byte j of x in bits 4j.. of the result's low half (the contigs' wire
+// format between ranks, kcount_ctgx.hip). A contig byte is ctg_byte's: code 0..4, quality 0 or 31, ten values in all, so
+// byte & 15 = code | (quality != 0) << 3 loses nothing: k_expand_nibbles' rule (v & 7) | ((v >> 3) * 0xF8) gives the byte back.
+MHM_HD uint32_t ctg_nib4(uint32_t x) {
+  const uint32_t y = x & 0x0f0f0f0fu;
+  const uint32_t t = y | (y >> 4);  // bytes 0 and 2 hold the pairs (0, 1) and (2, 3)
+  return (t & 0xffu) | ((t >> 8) & 0xff00u);
+}
+// Eight bytes (lo: the first four) as one dword of nibbles, the first byte in the lowest nibble.
+MHM_HD uint32_t ctg_nib8(uint32_t lo, uint32_t hi) { return ctg_nib4(lo) | (ctg_nib4(hi) << 16); }
+
 // Contig::get_uint16_t_depth of a Contig::depth (src/contigs.hpp:65): (uint16_t)(depth > 65535 ? 65535 : depth), that
 // is truncation toward zero, +inf -> 65535. A NaN or a negative depth has no defined conversion there: *ok = false.
 MHM_HD uint16_t ctg_depth_u16(double depth, bool *ok) {

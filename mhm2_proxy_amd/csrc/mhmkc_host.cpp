@@ -72,6 +72,7 @@ struct DebugKnobs {
   // merge_grid, the most workgroups of the read-pair merge's launches (0: their own grids), likewise lives where
   // fastq.hip's launches read it: mhm::merge_grid_cap (kcount_launch.hpp)
   // ctg_pack_grid, the most workgroups of the contig packing kernel (0: its own grid): mhm::ctg_pack_grid_cap
+  // ctgx_grid, the most workgroups of the multi-rank contig gather's kernels (0: their own grids): mhm::ctgx_grid_cap
 };
 DebugKnobs g_dbg;
 
@@ -746,6 +747,19 @@ struct mhmkc {
   std::vector<uint8_t> ctg_gbytes;
   std::vector<uint64_t> ctg_goffs, ctg_gwin;
   std::vector<uint16_t> ctg_gdepth;
+  // the same on the device, when a rank of the round gave contigs on the device: every rank's contigs
+  // in the contig pass's layout, gx_n contigs, gx_nb bytes, gx_w counted windows; freed when the finish ends
+  bool gx_on = false;
+  uint64_t gx_n = 0, gx_nb = 0, gx_w = 0;
+  DevBuf d_gx_bytes, d_gx_offs, d_gx_win, d_gx_depth;
+  mhmkc_ctg_ranks_info cinfo{};
+  int gather_ctgs_ranks();
+  int gather_ctgs_device(const std::vector<uint64_t> &sizes, std::vector<hipEvent_t> &evs);
+  void gx_drop() {
+    gx_on = false;
+    gx_n = gx_nb = gx_w = 0;
+    for (DevBuf *b : {&d_gx_bytes, &d_gx_offs, &d_gx_win, &d_gx_depth}) b->release();
+  }
   int handoff();
   int finish(uint64_t *n_out_ret);
   int finish_passes(uint64_t owned) const;
@@ -1884,6 +1898,222 @@ int mhmkc::gather_ctgs(std::vector<uint8_t> &gb, std::vector<uint64_t> &go, std:
   return MHMKC_OK;
 }
 
+// The round's contigs of all ranks, once per finish. The route is every rank's alike: it follows from
+// all-gathered values. No rank holds contigs on the device: gather_ctgs, through the host. Else every rank gathers on the
+// device (gather_ctgs_device), a rank with host contigs uploading them first.
+int mhmkc::gather_ctgs_ranks() {
+  const int g = G(), me = cfg.rank;
+  int rc;
+  gx_drop();
+  cinfo = mhmkc_ctg_ranks_info{};
+  const uint64_t mine[4] = {pc_on ? pc_n : (uint64_t)ctg_depth.size(), pc_on ? pc_nb : (uint64_t)ctg_bytes.size(),
+                            pc_on ? pc_w : ctg_win.back(), pc_on ? 1ull : 0ull};
+  std::vector<uint64_t> sizes(4 * (size_t)g, 0);
+  if ((rc = allgather_host(mine, sizes.data(), 32))) return rc;
+  if (memcmp(&sizes[4 * (size_t)me], mine, 32) != 0)
+    return fail(MHMKC_ETRANSPORT, "contig gather: the gathered sizes do not hold this rank's");
+  uint64_t n_all = 0, b_all = 0, w_all = 0, any_dev = 0;
+  for (int r = 0; r < g; r++) {
+    const uint64_t *s = &sizes[4 * (size_t)r];
+    if (s[0] >> 48 || s[1] >> 48 || s[2] >> 48)  // (so that no sum below wraps, on every rank alike)
+      return fail(MHMKC_EINVAL, "contig gather: rank %d announces %llu contigs, %llu bytes, %llu windows", r,
+                  (unsigned long long)s[0], (unsigned long long)s[1], (unsigned long long)s[2]);
+    n_all += s[0];
+    b_all += s[1];
+    w_all += s[2];
+    any_dev |= s[3];
+  }
+  if (!any_dev) {
+    if ((rc = gather_ctgs(ctg_gbytes, ctg_goffs, ctg_gwin, ctg_gdepth))) return rc;
+  } else {
+    if (w_all >= 0xffffffffull) return fail(MHMKC_EINVAL, "at most 2^32-1 contig k-mers per round");
+    if (n_all) {
+      std::vector<hipEvent_t> evs;
+      rc = gather_ctgs_device(sizes, evs);
+      if (rc) (void)hipStreamSynchronize(stream);
+      for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+      if (rc) {
+        gx_drop();
+        cinfo = mhmkc_ctg_ranks_info{};
+        return rc;
+      }
+    }
+  }
+  if (n_all) {
+    cinfo.n_ctgs = mine[0];
+    cinfo.n_bases = mine[1];
+    cinfo.n_ctgs_all = n_all;
+    cinfo.n_bases_all = b_all;
+    cinfo.windows_all = w_all;
+  }
+  return MHMKC_OK;
+}
+
+// The device route. Collectives, in this order on every rank: the allocation verdicts, the contigs, the status. Between
+// them a rank works alone; what fails there reaches the status exchange, and every rank returns an error.
+int mhmkc::gather_ctgs_device(const std::vector<uint64_t> &sizes, std::vector<hipEvent_t> &evs) {
+  const int g = G(), me = cfg.rank;
+  hipError_t e = hipSuccess;
+  int rc;
+  auto mark = [&]() -> int {
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return -1;
+    (void)hipEventRecord(ev, stream);
+    evs.push_back(ev);
+    return (int)evs.size() - 1;
+  };
+  auto ms = [&](int a, int b) -> double {
+    float f = 0;
+    if (a < 0 || b < 0 || hipEventElapsedTime(&f, evs[(size_t)a], evs[(size_t)b]) != hipSuccess) return 0;
+    return (double)f;
+  };
+  // tab = [the ranks' first contigs | their first bytes] (g + 1 each), as announced
+  std::vector<uint64_t> tab(2 * ((size_t)g + 1), 0);
+  uint64_t *base = tab.data(), *bst = tab.data() + g + 1;
+  uint64_t w_all = 0;
+  for (int r = 0; r < g; r++) {
+    base[r + 1] = base[r] + sizes[4 * (size_t)r];
+    bst[r + 1] = bst[r] + sizes[4 * (size_t)r + 1];
+    w_all += sizes[4 * (size_t)r + 2];
+  }
+  const uint64_t n_all = base[g], b_all = bst[g];
+  const uint64_t n_me = sizes[4 * (size_t)me], b_me = sizes[4 * (size_t)me + 1];
+
+  // 1. this rank's contigs on the device, the gathered buffers and the scratch: lengths of all ranks, this rank's
+  // nibbles, every peer's nibbles, the rank table, the mailbox, the scans' planes
+  DevBuf xs;
+  struct Release {
+    DevBuf &b;
+    ~Release() { b.release(); }
+  } xs_release{xs};
+  const size_t o_lens = 0, o_nib = align_up(n_all * 4 + 4, 256);
+  std::vector<size_t> o_peer((size_t)g + 1, 0);
+  o_peer[0] = o_nib + align_up((b_me + 1) / 2 + 8, 256);
+  for (int r = 0; r < g; r++)
+    o_peer[(size_t)r + 1] = o_peer[(size_t)r] + (r == me ? 0 : align_up((sizes[4 * (size_t)r + 1] + 1) / 2 + 8, 256));
+  const size_t o_tab = o_peer[(size_t)g], o_box = o_tab + align_up(16 * ((size_t)g + 1), 256);
+  const size_t o_tmp = o_box + 256, tmp_b = mhm::ctgx_tmp_bytes(n_all);
+  bool up_ok = true;
+  const std::string err0 = err;
+  if (!pc_on && n_me) up_ok = pc_begin() == MHMKC_OK;  // host contigs: uploaded, in their order
+  const std::string up_err = err;
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(e, "contig gather");
+  if ((e = d_gx_bytes.ensure(b_all + 64)) != hipSuccess || (e = d_gx_offs.ensure((n_all + 1) * 8)) != hipSuccess ||
+      (e = d_gx_win.ensure((n_all + 1) * 8)) != hipSuccess || (e = d_gx_depth.ensure(n_all * 2 + 2)) != hipSuccess ||
+      (e = xs.ensure(o_tmp + tmp_b)) != hipSuccess)
+    (void)hipGetLastError();
+  const uint64_t ok = up_ok && e == hipSuccess ? 1 : 0;
+  std::vector<uint64_t> oks((size_t)g, 0);
+  if ((rc = allgather_host(&ok, oks.data(), 8))) return rc;
+  for (int r = 0; r < g; r++)
+    if (!oks[(size_t)r]) {
+      if (r == me && !up_ok) return fail(MHMKC_ENOMEM, "contig gather: this rank could not upload its contigs: %s", up_err.c_str());
+      return fail(MHMKC_ENOMEM, "contig gather: rank %d could not allocate %llu contigs of %llu bytes", r,
+                  (unsigned long long)n_all, (unsigned long long)b_all);
+    }
+  err = err0;
+  char *x = xs.as<char>();
+  uint32_t *lens = (uint32_t *)(x + o_lens);
+  uint8_t *nib = (uint8_t *)(x + o_nib);
+  uint64_t *d_tab = (uint64_t *)(x + o_tab);
+  mhm::CtgxBox *d_box = (mhm::CtgxBox *)(x + o_box);
+  uint8_t *gbytes = d_gx_bytes.as<uint8_t>();
+  uint16_t *gdepth = d_gx_depth.as<uint16_t>();
+
+  // 2. the wire format of this rank's contigs; its own segment goes to its place on the device
+  const int t0 = mark();
+  int lrc = MHMKC_OK;
+  if ((e = mhm::launch_ctgx_begin(d_box, stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_tab, tab.data(), 8 * tab.size(), hipMemcpyHostToDevice, stream)) != hipSuccess ||
+      (n_me && (e = mhm::launch_ctgx_pack(d_pc_offs.as<uint64_t>(), n_me, d_pc_bytes.as<uint8_t>(), b_me, lens + base[me], nib,
+                                          d_box, stream)) != hipSuccess) ||
+      (n_me && (e = hipMemcpyAsync(gdepth + base[me], d_pc_depth.p, n_me * 2, hipMemcpyDeviceToDevice, stream)) != hipSuccess) ||
+      (b_me && (e = hipMemcpyAsync(gbytes + bst[me], d_pc_bytes.p, b_me, hipMemcpyDeviceToDevice, stream)) != hipSuccess))
+    lrc = hip_fail(e, "contig gather: pack");
+  const int t1 = mark();
+
+  // 3. to every peer 6 n + ceil(b / 2) bytes: u32 lengths, u16 depths, nibbles (what a failed pack left is sent all the
+  // same: the peers' receives are posted, and the status below fails the round)
+  std::vector<Xfer> snd, rcv;
+  for (int p = 0; p < g; p++) {
+    if (p == me) continue;
+    const uint64_t n_p = sizes[4 * (size_t)p], b_p = sizes[4 * (size_t)p + 1];
+    if (n_me) {
+      snd.push_back({p, lens + base[me], n_me * 4});
+      snd.push_back({p, d_pc_depth.p, n_me * 2});
+      snd.push_back({p, nib, (b_me + 1) / 2});
+    }
+    if (n_p) {
+      rcv.push_back({p, lens + base[p], n_p * 4});
+      rcv.push_back({p, gdepth + base[p], n_p * 2});
+      rcv.push_back({p, x + o_peer[(size_t)p], (b_p + 1) / 2});
+    }
+  }
+  const uint64_t sent0 = st.bytes_sent, recv0 = st.bytes_recv;
+  rc = move(snd, rcv);
+  const uint64_t sent = st.bytes_sent - sent0, recvd = st.bytes_recv - recv0;
+  st.bytes_sent = sent0;  // bytes_* count the record exchange only
+  st.bytes_recv = recv0;
+  if (rc) return rc;
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess && !lrc) lrc = hip_fail(e, "contig gather: move");
+  const int t2 = mark();
+
+  // 4. on this rank alone: offsets and window prefix from the lengths, the peers' bases to their places
+  int t3 = -1;
+  auto assemble = [&]() -> int {
+    hipError_t e2;
+    if ((e2 = mhm::launch_ctgx_assemble(lens, n_all, k, d_tab, g, d_gx_offs.as<uint64_t>(), d_gx_win.as<uint64_t>(),
+                                        x + o_tmp, tmp_b, d_box, stream)) != hipSuccess)
+      return hip_fail(e2, "contig gather: offsets");
+    for (int p = 0; p < g; p++)
+      if (p != me && (e2 = mhm::launch_expand_nibbles((const uint8_t *)(x + o_peer[(size_t)p]), gbytes, bst[p],
+                                                      bst[p + 1] - bst[p], stream)) != hipSuccess)
+        return hip_fail(e2, "contig gather: bases");
+    t3 = mark();
+    mhm::CtgxBox box;
+    if ((e2 = hipMemcpyAsync(&box, d_box, sizeof box, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e2 = hipStreamSynchronize(stream)) != hipSuccess)
+      return hip_fail(e2, "contig gather");
+    if (box.long_ctg != ~0ull) return fail(MHMKC_EINVAL, "at most 2^32-1 contig k-mers per round");
+    if (box.bad_rank != ~0ull)
+      return fail(MHMKC_ETRANSPORT, "contig gather: rank %llu's contig lengths do not sum to the %llu bytes it announced",
+                  box.bad_rank, (unsigned long long)(bst[box.bad_rank + 1] - bst[box.bad_rank]));
+    if (box.windows != w_all)
+      return fail(MHMKC_ETRANSPORT, "contig gather: %llu contig k-mers in the gathered lengths, the ranks announced %llu",
+                  box.windows, (unsigned long long)w_all);
+    return MHMKC_OK;
+  };
+  if (!lrc) lrc = assemble();
+  if (lrc) (void)hipStreamSynchronize(stream);
+
+  // 5. the status: a rank that failed alone fails every rank
+  const uint64_t bad = lrc ? 1 : 0;
+  std::vector<uint64_t> bads((size_t)g, 0);
+  const std::string lerr = err;
+  if ((rc = allgather_host(&bad, bads.data(), 8))) return rc;
+  if (lrc) {
+    err = lerr;
+    return lrc;
+  }
+  for (int r = 0; r < g; r++)
+    if (bads[(size_t)r]) return fail(MHMKC_ETRANSPORT, "contig gather: rank %d failed (its mhmkc_last_error says why)", r);
+  gx_on = true;
+  gx_n = n_all;
+  gx_nb = b_all;
+  gx_w = w_all;
+  cinfo.device_route = 1;
+  cinfo.bytes_sent = sent;
+  cinfo.bytes_recv = recvd;
+  cinfo.ms_pack = ms(t0, t1);
+  cinfo.ms_move = ms(t1, t2);
+  cinfo.ms_assemble = ms(t2, t3);
+  cinfo.ms_total = ms(t0, t3);
+  cinfo.gathered_bytes = d_gx_bytes.cap + d_gx_offs.cap + d_gx_win.cap + d_gx_depth.cap;
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return MHMKC_OK;
+}
+
 int mhmkc::prepare_ctgs() {
   ctg_n = 0;
   const std::vector<uint8_t> *cb_ = &ctg_bytes;
@@ -1891,20 +2121,24 @@ int mhmkc::prepare_ctgs() {
   const std::vector<uint16_t> *cd = &ctg_depth;
   if (G() > 1) {
     if (!ctg_gathered) {  // (collective: every rank gathers exactly once per finish)
-      int rc = gather_ctgs(ctg_gbytes, ctg_goffs, ctg_gwin, ctg_gdepth);
+      int rc = gather_ctgs_ranks();
       if (rc) return rc;
       ctg_gathered = true;
     }
     cb_ = &ctg_gbytes, co = &ctg_goffs, cw = &ctg_gwin, cd = &ctg_gdepth;
   }
-  const uint64_t W = pc_on ? pc_w : cw->back();
+  // the contigs the pass reads where they are, every time: the round's own (single rank) or the gathered copy
+  const bool dev = G() > 1 ? gx_on : pc_on;
+  const uint64_t W = !dev ? cw->back() : G() > 1 ? gx_w : pc_w;
   if (!W) return MHMKC_OK;
   hipError_t e;
-  const uint64_t nc = pc_on ? pc_n : cd->size();
-  // the round's contigs are on the device already (single rank): the contig pass reads them where they are, every time
+  const uint64_t nc = !dev ? cd->size() : G() > 1 ? gx_n : pc_n;
   mhm::CtgView cv{d_pc_bytes.as<uint8_t>(), d_pc_offs.as<uint64_t>(), d_pc_depth.as<uint16_t>(), d_pc_win.as<uint64_t>(),
                   nc, W};
-  if (!pc_on) {
+  if (dev && G() > 1)
+    cv = mhm::CtgView{d_gx_bytes.as<uint8_t>(), d_gx_offs.as<uint64_t>(), d_gx_depth.as<uint16_t>(),
+                      d_gx_win.as<uint64_t>(), nc, W};
+  if (!dev) {
     if ((e = grow(d_ctg_bytes, cb_->size() + 64)) != hipSuccess || (e = grow(d_ctg_offs, (nc + 1) * 8)) != hipSuccess ||
         (e = grow(d_ctg_win, (nc + 1) * 8)) != hipSuccess || (e = grow(d_ctg_depth, nc * 2 + 2)) != hipSuccess)
       return hip_fail(e, "contig staging");
@@ -3232,6 +3466,7 @@ void mhmkc_destroy(mhmkc_t h) {
                      &h->d_ctg_keys[2], &h->d_ctg_keys[3]};
   for (DevBuf *b : cbufs) b->release();
   h->pc_drop();
+  h->gx_drop();
   h->x_send.release();
   h->x_recv.release();
   h->fq_file_buf.release();
@@ -3906,7 +4141,8 @@ int mhmkc::add_ctgs_dev(const char *d_seqs, const uint64_t *d_offs, const void *
 int mhmkc_add_ctgs_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const void *d_depths, int depth_type,
                           uint64_t n_ctgs, uint64_t n_bases) {
   if (!h) return MHMKC_EINVAL;
-  if (h->cfg.n_ranks > 1) return h->fail(MHMKC_EUNSUPPORTED, "device contigs: single-rank handles only");
+  if (h->cfg.n_ranks > 1 && h->cfg.output_owner != MHMKC_OWNER_MINIMIZER)
+    return h->fail(MHMKC_EUNSUPPORTED, "device contigs on several ranks: MHMKC_OWNER_MINIMIZER handles only");
   if (h->finished) return h->fail(MHMKC_ESTATE, "handle already finished; call mhmkc_reset first");
   if (depth_type != MHMKC_DEPTH_U16 && depth_type != MHMKC_DEPTH_F64) return h->fail(MHMKC_EINVAL, "unknown depth_type");
   if (n_ctgs && (!d_seq_offsets || !d_depths || (n_bases && !d_seqs))) return h->fail(MHMKC_EINVAL, "null device buffer");
@@ -3918,7 +4154,8 @@ static int uutigs_need(mhmkc_t h);
 int mhmkc_add_ctgs_from(mhmkc_t h, mhmkc_t src) {
   if (!h) return MHMKC_EINVAL;
   if (!src) return h->fail(MHMKC_EINVAL, "null source handle");
-  if (h->cfg.n_ranks > 1) return h->fail(MHMKC_EUNSUPPORTED, "device contigs: single-rank handles only");
+  if (h->cfg.n_ranks > 1 && h->cfg.output_owner != MHMKC_OWNER_MINIMIZER)
+    return h->fail(MHMKC_EUNSUPPORTED, "device contigs on several ranks: MHMKC_OWNER_MINIMIZER handles only");
   if (h->finished) return h->fail(MHMKC_ESTATE, "handle already finished; call mhmkc_reset first");
   if (src->dev != h->dev) return h->fail(MHMKC_EINVAL, "the handles are on different devices");
   int rc = uutigs_need(src);  // built now if the finished source has none yet; its own multi-rank / state errors
@@ -3976,7 +4213,12 @@ int mhmkc_minimizer_hashes(mhmkc_t h, const uint64_t *keys, uint64_t n, int32_t 
 
 int mhmkc_finish(mhmkc_t h, uint64_t *n_out) {
   if (!h) return MHMKC_EINVAL;
-  return h->finish(n_out);
+  const int rc = h->finish(n_out);
+  if (h->d_gx_bytes.p) {  // the gathered contigs of all ranks served this finish only (the count has read them)
+    h->gx_drop();
+    h->st.device_bytes = g_dev_live.load();
+  }
+  return rc;
 }
 
 int mhmkc_fetch(mhmkc_t h, uint64_t *keys, uint16_t *counts, char *left, char *right) {
@@ -4814,6 +5056,12 @@ int mhmkc_uutigs_ranks_info(mhmkc_t h, mhmkc_uutig_ranks_info *info) {
   return MHMKC_OK;
 }
 
+int mhmkc_ctgs_ranks_info(mhmkc_t h, mhmkc_ctg_ranks_info *info) {
+  if (!h || !info) return MHMKC_EINVAL;
+  *info = h->cinfo;
+  return MHMKC_OK;
+}
+
 int mhmkc_get_stats(mhmkc_t h, mhmkc_stats *s) {
   if (!h || !s) return MHMKC_EINVAL;
   *s = h->st;
@@ -4847,6 +5095,8 @@ int mhmkc_reset(mhmkc_t h) {
   h->ctg_n = 0;
   const bool had_pc = h->pc_on;
   h->pc_drop();
+  h->gx_drop();
+  h->cinfo = mhmkc_ctg_ranks_info{};
   h->fq_reads = h->fq_bases = 0;
   h->finished = false;
   h->began = false;
@@ -4897,6 +5147,7 @@ int mhmkc_debug_set(const char *knob, int64_t value) {
   else if (k == "query_grid") mhm::query_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else if (k == "merge_grid") mhm::merge_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else if (k == "ctg_pack_grid") mhm::ctg_pack_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
+  else if (k == "ctgx_grid") mhm::ctgx_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else return MHMKC_EINVAL;
   return MHMKC_OK;
 }
@@ -4906,6 +5157,7 @@ void mhmkc_debug_reset(void) {
   mhm::query_grid_cap = 0;
   mhm::merge_grid_cap = 0;
   mhm::ctg_pack_grid_cap = 0;
+  mhm::ctgx_grid_cap = 0;
 }
 
 int mhmkc_debug_nib_pack(const uint8_t *src, uint64_t n, uint8_t *dst, int qcut, int mode) {

@@ -385,7 +385,10 @@ class KmerCounter:
         """add_ctgs with device-resident torch tensors (mhmkc_add_ctgs_device): uint8 ASCII bases back to back,
         int64/uint64 offsets with n_ctgs + 1 entries, one depth per contig as float64 (a Contig::depth, converted as
         Contig::get_uint16_t_depth() does) or uint16. The tensors are read during the call only. n_bases defaults
-        to the bases tensor's size; the library checks it against offsets_t[-1] on the device."""
+        to the bases tensor's size; the library checks it against offsets_t[-1] on the device.
+        On a counter of several ranks (MHMKC_OWNER_MINIMIZER only) the call is local: every rank passes its own contigs,
+        possibly none, ranks may mix this with add_ctgs, and finish() gathers the contigs of all ranks on the device, in
+        rank order (ctgs_ranks_info())."""
         import torch
 
         n_ctgs = int(offsets_t.numel()) - 1
@@ -415,8 +418,18 @@ class KmerCounter:
     def add_ctgs_from(self, other: "KmerCounter") -> None:
         """The uutigs of a finished counter as this round's contigs, handed over on the device (mhmkc_add_ctgs_from):
         the step from one contigging round to the next k (src/contigging.cpp:93-158). The uutigs are built first if
-        `other` has none yet."""
+        `other` has none yet. Several ranks (MHMKC_OWNER_MINIMIZER): after other.uutigs_ranks() on every rank, every rank
+        hands over its own part of that build; finish() gathers the parts on the device (ctgs_ranks_info())."""
         self._check(N.lib().mhmkc_add_ctgs_from(self._h, other._h))
+
+    def ctgs_ranks_info(self) -> dict:
+        """How the contigs of the last finish() of a counter of several ranks reached every rank
+        (mhmkc_ctgs_ranks_info): device_route (1: gathered on the device), this rank's and the round's sizes, the bytes this
+        rank sent and received, stage times (device events) and the memory of the gathered copy. All zeros before such a
+        finish with contigs."""
+        info = N.MhmkcCtgRanksInfo()
+        self._check(N.lib().mhmkc_ctgs_ranks_info(self._h, C.byref(info)))
+        return info.as_dict()
 
     # -- ranks, thresholds
     def set_transport(self, transport: "TorchDistTransport") -> None:
