@@ -503,6 +503,76 @@ typedef struct {
 } mhmkc_uutig_ranks_info;
 int mhmkc_uutigs_ranks_info(mhmkc_t h, mhmkc_uutig_ranks_info *info);
 
+/* Queries answered by the rank that owns the key, and every row's de Bruijn links with neighbours on any rank
+ * (DESIGN.md §3.11b). The reference's traversal computes get_kmer_target_rank of a neighbour and asks that rank by rpc
+ * (src/dbjg_traversal.cpp:228-236,260-274, src/kcount/kmer_dht.cpp:193-219); here every rank hands over a batch, the
+ * batches are grouped by owner on the GPUs, travel over the handle's transport (RCCL or mhmkc_set_transport), are
+ * answered from the owner's own index and travel back. A rank holds state proportional to its own rows: nothing of
+ * another rank's table is kept or indexed.
+ * Both calls are collective over the ranks of a finished MHMKC_OWNER_MINIMIZER handle: every rank calls them, in the same
+ * order. The work goes in rounds of at most MHMKC_ROUTE_CHUNK queries per rank (an environment variable read at the
+ * call, default 2^22, at most 2^30); the number of rounds is the largest over the ranks, so a rank with fewer queries
+ * (or none) takes part with empty rounds. A round's device scratch is at most chunk * (8 NL + 13) bytes for the asking
+ * side, with NL = k / 32 + 1, plus (8 NL + 8) bytes per query received; all of it is freed before the call returns.
+ * n_ranks == 1: the single-rank call, with rank 0. n_ranks > 1 with MHMKC_OWNER_HASH: MHMKC_EUNSUPPORTED; before
+ * finish: MHMKC_ESTATE; both before any collective, in that order. A rank that cannot allocate gives MHMKC_ENOMEM on
+ * every rank before a byte of that round moves; any other failure on one rank after the first collective is a failure
+ * on every rank: MHMKC_ETRANSPORT on the ranks that did not fail themselves. */
+#define MHMKC_NO_RANK 0xFFu
+
+/* mhmkc_lookup for keys that may live on any rank (get_kmer_target_rank + the rpc to get_local_kmer_counts,
+ * src/kcount/kmer_dht.cpp:193-219, src/dbjg_traversal.cpp:228-236). Every rank gives its own n (0 is allowed, with NULL
+ * arrays). Query i is canonicalized or not exactly as in mhmkc_lookup. ranks[i] = get_kmer_target_rank of the key that
+ * is looked up, always set, on a miss too (a key and its reverse complement have the same owner); rows[i], counts[i],
+ * left[i], right[i] are what mhmkc_lookup on that rank's handle returns for the key: rows[i] is the row there, a miss
+ * gives MHMKC_NO_ROW and zeros. Any output pointer may be NULL. Host arrays. */
+int mhmkc_lookup_ranks(mhmkc_t h, const uint64_t *keys, uint64_t n, int canonicalize, uint8_t *ranks, uint32_t *rows,
+                       uint16_t *counts, char *left, char *right);
+/* The same with device arrays, on the handle's stream; the outputs are complete when the call returns. */
+int mhmkc_lookup_ranks_device(mhmkc_t h, const uint64_t *d_keys, uint64_t n, int canonicalize, uint8_t *d_ranks,
+                              uint32_t *d_rows, uint16_t *d_counts, char *d_left, char *d_right);
+
+/* mhmkc_dbjg_links with the neighbour looked up on its target rank (get_next_step at rank_n() > 1,
+ * src/dbjg_traversal.cpp:165-239,260-274). Entry d * n_out + i follows the three rules of mhmkc_dbjg_links unchanged, in
+ * their order; in step 2 the neighbour is asked of get_kmer_target_rank(neighbour). next_rank / next_row name that rank
+ * and the row there; where the single-rank call gives next = MHMKC_NO_ROW they are MHMKC_NO_RANK and MHMKC_NO_ROW.
+ * Built by the first call after a finish (a collective) and kept on the device until the next reset / finish / destroy: 6
+ * bytes per entry, 12 per row, counted in mhmkc_stats.device_bytes[_peak]; a later call returns the kept arrays and
+ * runs no collective. Only a rank's own rows are limited to 2^32-2; the union of the ranks' tables is not. */
+int mhmkc_dbjg_links_ranks(mhmkc_t h);
+/* Host copies of the kept arrays, 2 * n_out entries each (any may be NULL); builds them first if needed, and is then
+ * the collective. */
+int mhmkc_dbjg_links_ranks_fetch(mhmkc_t h, uint8_t *next_rank, uint32_t *next_row, uint8_t *status);
+/* The kept arrays on the device (builds them first if needed; NULL pointers for a rank without rows). */
+int mhmkc_dbjg_links_ranks_device(mhmkc_t h, const uint8_t **d_next_rank, const uint32_t **d_next_row,
+                                  const uint8_t **d_status);
+
+/* How the last of the two collectives on this handle went (a call answered from the kept links changes nothing). A
+ * query is one key asked of its owner; a link entry that its own row ends asks nothing. (The struct carries a _t, unlike
+ * its sibling info structs, because the call is named mhmkc_route_info and C keeps types and functions in one name
+ * space.) */
+enum { MHMKC_ROUTE_ROUTE = 0, MHMKC_ROUTE_EXCHANGE = 1, MHMKC_ROUTE_ANSWER = 2, MHMKC_ROUTE_RETURN = 3,
+       MHMKC_ROUTE_UNPACK = 4, MHMKC_ROUTE_STAGES = 5 };
+typedef struct {
+  uint64_t rounds;          /* rounds of the call, the largest need over the ranks */
+  uint64_t chunk;           /* queries per rank and round (MHMKC_ROUTE_CHUNK) */
+  uint64_t entries;         /* what this rank handed over: the batch's n, or 2 * n_out link entries */
+  uint64_t queries;         /* queries this rank asked (entries minus those that ask nothing) */
+  uint64_t queries_local;   /* of them, answered by this rank itself: they never touch the transport */
+  uint64_t queries_sent;    /* of them, sent to other ranks (queries_local + queries_sent == queries) */
+  uint64_t queries_recv;    /* queries of other ranks answered here */
+  uint64_t bytes_sent;      /* 8 NL per query sent + 8 per reply to a query received */
+  uint64_t bytes_recv;      /* 8 NL per query received + 8 per reply to a query sent */
+  double ms_stage[MHMKC_ROUTE_STAGES]; /* device events on the handle's stream, summed over the rounds: owners and
+                               histogram; pack + the queries' move; the answers; the replies' move; unpack / verdicts
+                               (the moves include their host staging under mhmkc_set_transport and the wait for the
+                               slowest rank) */
+  double ms_total;          /* wall time of the call */
+  uint64_t scratch_bytes;   /* the peak of the call's device scratch (asking side + received queries and replies) */
+  uint64_t kept_bytes;      /* what stays on the device: the links of mhmkc_dbjg_links_ranks, else 0 */
+} mhmkc_route_info_t;
+int mhmkc_route_info(mhmkc_t h, mhmkc_route_info_t *info);
+
 /* Host-staged exchange between ranks (instead of RCCL): for n_ranks > 1 with comm_id == NULL, set before
  * the first mhmkc_finish. Every rank's callbacks are called collectively, in the same order on all ranks, with
  * host buffers; a callback returns 0 on success.

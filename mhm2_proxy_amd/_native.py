@@ -33,6 +33,7 @@ MHMKC_OWNER_HASH = 0
 MHMKC_OWNER_MINIMIZER = 1
 
 MHMKC_NO_ROW = 0xFFFFFFFF
+MHMKC_NO_RANK = 0xFF
 MHMKC_LINK_OK, MHMKC_LINK_DEADEND, MHMKC_LINK_FORK, MHMKC_LINK_CONFLICT, MHMKC_LINK_RC = 0, 1, 2, 3, 0x80
 
 STAGES = ["tileidx", "extract_hist", "extract_scatter", "exchange", "part_hist", "part_scatter", "count", "other"]
@@ -53,10 +54,13 @@ ABI_SYMBOLS = [
     "mhmkc_uutigs", "mhmkc_uutigs_fetch", "mhmkc_uutigs_device", "mhmkc_uutig_rows", "mhmkc_uutig_rows_device",
     "mhmkc_uutigs_info", "mhmkc_uutigs_ranks", "mhmkc_uutigs_ranks_info",
     "mhmkc_add_ctgs_device", "mhmkc_add_ctgs_from", "mhmkc_ctgs_ranks_info",
+    "mhmkc_lookup_ranks", "mhmkc_lookup_ranks_device", "mhmkc_dbjg_links_ranks", "mhmkc_dbjg_links_ranks_fetch",
+    "mhmkc_dbjg_links_ranks_device", "mhmkc_route_info",
 ]
 MHMKC_DEPTH_U16, MHMKC_DEPTH_F64 = 0, 1
 UUTIG_MAX_ROUNDS = 48
 URANKS_STAGES = ("gather", "build", "select")  # MHMKC_URANKS_*
+ROUTE_STAGES = ("route", "exchange", "answer", "return", "unpack")  # MHMKC_ROUTE_*
 SYNTH_SYMBOLS = ["mhmkc_synth_config_init", "mhmkc_synth_genome", "mhmkc_synth_reads"]
 # the test-only entry point (include/mhmkc_debug.h)
 DEBUG_SYMBOLS = ["mhmkc_debug_examine4", "mhmkc_debug_nib_pack", "mhmkc_debug_reset", "mhmkc_debug_set"]
@@ -88,6 +92,19 @@ class MhmkcUutigRanksInfo(C.Structure):
         d = {f: getattr(self, f) for f, t in self._fields_ if t in (C.c_uint64, C.c_double)}
         for f in self._PER_STAGE + ("ms_stage",):
             d[f] = dict(zip(URANKS_STAGES, list(getattr(self, f))))
+        return d
+
+
+class MhmkcRouteInfo(C.Structure):
+    """mhmkc_route_info_t (include/mhmkc.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("rounds", "chunk", "entries", "queries", "queries_local", "queries_sent",
+                                          "queries_recv", "bytes_sent", "bytes_recv")] + \
+               [("ms_stage", C.c_double * len(ROUTE_STAGES)), ("ms_total", C.c_double),
+                ("scratch_bytes", C.c_uint64), ("kept_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, t in self._fields_ if t in (C.c_uint64, C.c_double)}
+        d["ms_stage"] = dict(zip(ROUTE_STAGES, list(self.ms_stage)))
         return d
 
 
@@ -308,6 +325,12 @@ def lib() -> C.CDLL:
     L.mhmkc_uutigs_ranks.argtypes = [VP, P(U64), P(U64), P(U64), P(U64)]
     L.mhmkc_uutigs_ranks_info.argtypes = [VP, P(MhmkcUutigRanksInfo)]
     L.mhmkc_ctgs_ranks_info.argtypes = [VP, P(MhmkcCtgRanksInfo)]
+    L.mhmkc_lookup_ranks.argtypes = [VP, VP, U64, I32, VP, VP, VP, VP, VP]
+    L.mhmkc_lookup_ranks_device.argtypes = [VP, VP, U64, I32, VP, VP, VP, VP, VP]
+    L.mhmkc_dbjg_links_ranks.argtypes = [VP]
+    L.mhmkc_dbjg_links_ranks_fetch.argtypes = [VP, VP, VP, VP]
+    L.mhmkc_dbjg_links_ranks_device.argtypes = [VP, P(VP), P(VP), P(VP)]
+    L.mhmkc_route_info.argtypes = [VP, P(MhmkcRouteInfo)]
     _lib = L
     return L
 

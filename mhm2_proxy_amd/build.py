@@ -31,11 +31,11 @@ ORACLE = ROOT / "oracle" / "liboracle.so"
 
 LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kcount_ctgin.hip", CSRC / "kcount_ctgx.hip",
                CSRC / "kcount_owner.hip",
-               CSRC / "kcount_query.hip",
+               CSRC / "kcount_query.hip", CSRC / "kcount_route.hip",
                CSRC / "kcount_uutig.hip", CSRC / "kcount_uutig_ranks.hip",
                CSRC / "fastq.hip",
                CSRC / "mhmkc_host.cpp"]
-LIB_DEPS = LIB_SOURCES + [CSRC / "kcount_launch.hpp", CSRC / "kmer_ops.hpp", ROOT / "include" / "mhmkc.h"]
+LIB_DEPS = LIB_SOURCES + [CSRC / "kcount_launch.hpp", CSRC / "kcount_query_dev.hpp", CSRC / "kmer_ops.hpp", ROOT / "include" / "mhmkc.h"]
 SYNTH_DEPS = [CSRC / "synth.c", ROOT / "include" / "mhmkc_synth.h"]
 FILL = ROOT / "tools" / "bin" / "kmermap_fill"
 FILL_DEPS = [ROOT / "tools" / "cpp" / "kmermap_fill.cpp", ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]

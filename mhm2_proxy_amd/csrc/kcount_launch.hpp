@@ -497,6 +497,43 @@ hipError_t launch_query_lookup(const uint64_t *q, uint64_t n, bool canonicalize,
 hipError_t launch_dbjg_links(const OutRows &t, uint64_t n, int k, int nl, int nlo, const QueryIndex &ix, uint32_t *next,
                              uint8_t *status, hipStream_t s);
 
+// Queries answered by the rank that owns the key (kcount_route.hip). A round serves m queries of one
+// rank, given as keys (links = 0: q holds m * nlo words, canonicalize as in launch_query_lookup) or as the link entries
+// [e0, e0 + m) of the rank's table t of n_rows rows (links = 1: entry d * n_rows + i asks for row i's neighbour in
+// direction d, or for nothing when the row's own extensions end it).
+struct RouteSource {
+  int links;
+  const uint64_t *q;
+  int canonicalize;
+  OutRows t;
+  uint64_t n_rows, e0;
+};
+hipError_t preload_route_kernels();
+// dest[i] = get_kmer_target_rank of query i (0xFF: the entry asks nothing); hist[r] += the queries of owner r (zero first)
+hipError_t launch_route(const RouteSource &src, uint64_t m, int k, int nl, int nlo, int mlen, int n_ranks, uint8_t *dest,
+                        unsigned long long *hist, hipStream_t s);
+// send: the queries' keys, nl words each, grouped by owner from cursor[r] on (cursor = the owners' first places, advanced
+// by the kernel); pos[i] = the place of query i in that layout (0xFFFFFFFF: none). send and the replies hold m places.
+hipError_t launch_route_pack(const RouteSource &src, uint64_t m, int k, int nl, int nlo, const uint8_t *dest, int n_ranks,
+                             unsigned long long *cursor, uint64_t *send, uint32_t *pos, hipStream_t s);
+// reply[i] = row | count << 32 | left << 48 | right << 56 of key i (nl words each) in the table ix indexes, a miss
+// 0xFFFFFFFF; ix.n_rows == 0: no index, every key misses
+hipError_t launch_route_answer(const uint64_t *keys, uint64_t n, int k, int nl, int nlo, const QueryIndex &ix,
+                               const OutRows &t, unsigned long long *reply, hipStream_t s);
+// the outputs of mhmkc_lookup_ranks for the round's m queries from reply[pos[i]] (any output may be null). layout: the
+// places of reply; n_rows_of [n_ranks]: the ranks' row counts; a place or a row beyond them reads as a miss
+hipError_t launch_route_unpack(const unsigned long long *reply, const uint32_t *pos, const uint8_t *dest, uint64_t m,
+                               uint64_t layout, int n_ranks, const unsigned long long *n_rows_of, uint8_t *ranks,
+                               uint32_t *rows, uint16_t *counts, char *left, char *right, hipStream_t s);
+// entries [e0, e0 + m) of next_rank / next_row / status [2 * n_rows] (mhmkc_dbjg_links_ranks)
+hipError_t launch_route_verdict(const RouteSource &src, uint64_t m, int k, int nl, int nlo,
+                                const unsigned long long *reply, const uint32_t *pos, const uint8_t *dest, uint64_t layout,
+                                int n_ranks, const unsigned long long *n_rows_of, uint8_t *next_rank, uint32_t *next_row,
+                                uint8_t *status, hipStream_t s);
+
+// one rank: next_rank[i] = 0 where next[i] names a row, else 0xFF (mhmkc_dbjg_links_ranks on a single-rank handle)
+hipError_t launch_route_rank0(const uint32_t *next, uint64_t n, uint8_t *next_rank, hipStream_t s);
+
 // The uutigs of the table from those links (kcount_uutig.hip). Port 2 * row + d; a port's ranking state:
 // link = the port reached (bits 0-39) | the round that wrote it (bits 48-55) | done (bit 63: the port is the chain's end
 // port), dist / sum / minw0, minrow = the rows passed, their counts, the smallest key among them.

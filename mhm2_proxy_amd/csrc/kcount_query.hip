@@ -15,6 +15,7 @@
 #include "../../include/mhmkc.h"
 
 #include "kcount_launch.hpp"
+#include "kcount_query_dev.hpp"
 #include "kmer_ops.hpp"
 
 namespace mhm {
@@ -22,34 +23,10 @@ namespace mhm {
 namespace {
 
 constexpr int Q_THREADS = 256;
-constexpr unsigned long long SLOT_EMPTY = ~0ull;
-constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
+constexpr unsigned long long SLOT_EMPTY = QSLOT_EMPTY;
+constexpr uint32_t NO_ROW = Q_NO_ROW;
 
 inline unsigned grid_for(uint64_t n) { return query_grid_for(n); }
-
-// mhmkc_map_hash of a key whose first NL words are w and whose other nlo - NL words are zero (the output rows'
-// layout for n_longs > k/32 + 1)
-template <int NL>
-__device__ __forceinline__ uint64_t key_hash(const uint64_t *w, int nlo) {
-  uint64_t h = 0x9E3779B97F4A7C15ull;
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-    h = (h ^ w[i]) * 0xBF58476D1CE4E5B9ull;
-    h ^= h >> 31;
-  }
-  for (int i = NL; i < nlo; i++) {
-    h *= 0xBF58476D1CE4E5B9ull;
-    h ^= h >> 31;
-  }
-  h *= 0x94D049BB133111EBull;
-  return h ^ (h >> 29);
-}
-
-template <int NL>
-__device__ __forceinline__ void load_key(const uint64_t *keys, uint64_t i, int nlo, uint64_t *w) {
-#pragma unroll
-  for (int j = 0; j < NL; j++) w[j] = keys[i * (uint64_t)nlo + j];
-}
 
 template <int NL>
 __global__ __launch_bounds__(Q_THREADS) void k_query_build(const uint64_t *keys, uint64_t n, int nlo, QueryIndex ix) {
@@ -64,27 +41,6 @@ __global__ __launch_bounds__(Q_THREADS) void k_query_build(const uint64_t *keys,
   }
 }
 
-// The row holding key w (NL words, the unused bits zero), or NO_ROW.
-template <int NL>
-__device__ __forceinline__ uint32_t find_row(const uint64_t *w, int nlo, const QueryIndex &ix, const uint64_t *keys) {
-  const uint64_t h = key_hash<NL>(w, nlo);
-  const uint32_t tag = (uint32_t)h;
-  uint64_t s = h >> ix.shift;
-  for (uint64_t probes = 0; probes <= ix.mask; probes++) {
-    const unsigned long long v = ix.slots[s];
-    const uint32_t row = (uint32_t)v;
-    if (row == NO_ROW) return NO_ROW;
-    if ((uint32_t)(v >> 32) == tag && (uint64_t)row < ix.n_rows) {
-      bool eq = true;
-#pragma unroll
-      for (int j = 0; j < NL; j++) eq &= keys[(uint64_t)row * nlo + j] == w[j];
-      if (eq) return row;
-    }
-    s = (s + 1) & ix.mask;
-  }
-  return NO_ROW;
-}
-
 template <int NL>
 __global__ __launch_bounds__(Q_THREADS) void k_query_lookup(const uint64_t *q, uint64_t n, int canonicalize, int k, int nlo,
                                                             QueryIndex ix, OutRows t, uint32_t *rows, uint16_t *counts,
@@ -92,15 +48,7 @@ __global__ __launch_bounds__(Q_THREADS) void k_query_lookup(const uint64_t *q, u
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t w[NL];
     load_key<NL>(q, i, nlo, w);
-    w[NL - 1] &= top_mask(k - 32 * (NL - 1));
-    if (canonicalize) {
-      uint64_t rc[NL];
-      revcomp<NL>(w, rc, k);
-      if (kmer_less<NL>(rc, w)) {
-#pragma unroll
-        for (int j = 0; j < NL; j++) w[j] = rc[j];
-      }
-    }
+    query_key<NL>(w, k, canonicalize);
     const uint32_t row = find_row<NL>(w, nlo, ix, t.keys);
     const bool hit = row != NO_ROW;
     if (rows) rows[i] = row;
@@ -109,13 +57,6 @@ __global__ __launch_bounds__(Q_THREADS) void k_query_lookup(const uint64_t *q, u
     if (right) right[i] = hit ? t.right[row] : (char)0;
   }
 }
-
-__device__ __forceinline__ uint32_t base_code(char c) {  // set_kmer's bit trick (src/kmer.cpp:274-296)
-  const uint32_t x = ((uint32_t)c & 4u) >> 1;
-  return x + ((x ^ ((uint32_t)c & 2u)) >> 1);
-}
-__device__ __forceinline__ char base_char(uint32_t code) { return (char)((0x54474341u >> (8 * code)) & 0xffu); }
-__device__ __forceinline__ char comp_char(char c) { return base_char(3u - base_code(c)); }
 
 // Entry d * n + i: row i's neighbour in direction d (0 LEFT, 1 RIGHT) in row i's stored orientation, with the checks of
 // get_next_step in its order, without the visited state.
@@ -126,52 +67,18 @@ __global__ __launch_bounds__(Q_THREADS) void k_dbjg_links(OutRows t, uint64_t n,
   for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (uint64_t)gridDim.x * blockDim.x) {
     const bool right_dirn = e >= n;
     const uint64_t i = right_dirn ? e - n : e;
-    const char l = t.left[i], r = t.right[i];
     uint32_t nx = NO_ROW;
     uint8_t st;
-    if (l == 'X' || r == 'X') {
-      st = MHMKC_LINK_DEADEND;
-    } else if (l == 'F' || r == 'F') {
-      st = MHMKC_LINK_FORK;
-    } else {
-      uint64_t w[NL], nb[NL], rc[NL];
-      load_key<NL>(t.keys, i, nlo, w);
-      const int kl = k - 32 * (NL - 1);  // bases in the last word
-      uint32_t back_check;               // the base the neighbour's extension must lead back to
-      if (right_dirn) {                  // forward_base(right), back-check against front()
-#pragma unroll
-        for (int j = 0; j < NL; j++) nb[j] = (w[j] << 2) | (j + 1 < NL ? w[j + 1] >> 62 : 0ull);
-        nb[NL - 1] |= (uint64_t)base_code(r) << (64 - 2 * kl);
-        back_check = (uint32_t)(w[0] >> 62);
-      } else {  // backward_base(left), back-check against back()
-#pragma unroll
-        for (int j = NL - 1; j >= 0; j--) nb[j] = (w[j] >> 2) | (j > 0 ? w[j - 1] << 62 : 0ull);
-        nb[0] |= (uint64_t)base_code(l) << 62;
-        nb[NL - 1] &= top_mask(kl);
-        back_check = (uint32_t)(w[NL - 1] >> (64 - 2 * kl)) & 3u;
-      }
-      revcomp<NL>(nb, rc, k);
-      const bool is_rc = kmer_less<NL>(rc, nb);
-      const uint32_t j = find_row<NL>(is_rc ? rc : nb, nlo, ix, t.keys);
+    uint64_t key[NL];
+    bool is_rc;
+    uint32_t back_check;
+    if (link_neighbour<NL>(t, i, right_dirn, k, nlo, key, is_rc, back_check, st)) {
+      const uint32_t j = find_row<NL>(key, nlo, ix, t.keys);
       if (j == NO_ROW) {
         st = MHMKC_LINK_DEADEND;
       } else {
         nx = j;
-        char jl = t.left[j], jr = t.right[j];
-        if (jl == 'X' || jr == 'X') {
-          st = MHMKC_LINK_DEADEND;
-        } else if (jl == 'F' || jr == 'F') {
-          st = MHMKC_LINK_FORK;
-        } else {
-          if (is_rc) {
-            const char tmp = jl;
-            jl = comp_char(jr);
-            jr = comp_char(tmp);
-          }
-          const char want = base_char(back_check);
-          const bool ok = right_dirn ? jl == want : jr == want;
-          st = ok ? (uint8_t)(MHMKC_LINK_OK | (is_rc ? MHMKC_LINK_RC : 0)) : (uint8_t)MHMKC_LINK_CONFLICT;
-        }
+        st = link_verdict(t.left[j], t.right[j], is_rc, right_dirn, back_check);
       }
     }
     next[e] = nx;

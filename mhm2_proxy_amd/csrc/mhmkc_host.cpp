@@ -523,6 +523,28 @@ struct mhmkc {
     d_ursel.release();
     d_urk.release();
   }
+  // queries routed to the owner rank (kcount_route.hip). d_rt_ask (a round's send layout, replies,
+  // places, owners, the per-rank tables) and d_rt_recv (the received queries and their replies) are one call's scratch;
+  // d_rlinks keeps mhmkc_dbjg_links_ranks's arrays (next_row u32, next_rank u8, status u8, 2 n_out entries each) until
+  // drop_route (reset, the next finish, destroy)
+  DevBuf d_rt_ask, d_rt_recv, d_rlinks;
+  bool rlinks_ready = false;
+  mhmkc_route_info_t rinfo{};
+  int route_rounds(bool links, const uint64_t *d_keys, uint64_t n, int canonicalize, uint8_t *d_ranks, uint32_t *d_rows,
+                   uint16_t *d_counts, char *d_left, char *d_right, int pre_rc);
+  int route_run(bool links, const uint64_t *d_keys, uint64_t n, int canonicalize, uint8_t *d_ranks, uint32_t *d_rows,
+                uint16_t *d_counts, char *d_left, char *d_right, int pre_rc, hipEvent_t *ev);
+  int dbjg_links_ranks();
+  uint32_t *rl_row() const { return d_rlinks.as<uint32_t>(); }
+  uint8_t *rl_rank() const { return (uint8_t *)(d_rlinks.as<char>() + align_up(n_out * 8, 256)); }
+  uint8_t *rl_status() const { return rl_rank() + align_up(n_out * 2, 256); }
+  void drop_route() {
+    d_rt_ask.release();
+    d_rt_recv.release();
+    d_rlinks.release();
+    rlinks_ready = false;
+    rinfo = mhmkc_route_info_t{};
+  }
   void drop_query() {
     drop_uranks_scratch();
     uranks_ready = false;
@@ -2628,6 +2650,7 @@ int mhmkc::finish(uint64_t *n_out_ret) {
   if (rc) return rc;
   ord_ready = false;
   drop_query();
+  drop_route();
   ctg_gathered = false;
   if ((rc = resolve_slabs())) return rc;
   hipError_t e;
@@ -3396,6 +3419,7 @@ int mhmkc_create(mhmkc_t *out, const mhmkc_config *cfg) {
   }
   (void)mhm::preload_owner_kernels();  // (the hand-off's code object: loaded here, not in the first fetch)
   (void)mhm::preload_query_kernels();  // (and the query kernels': not in the first lookup)
+  if (cfg->n_ranks > 1) (void)mhm::preload_route_kernels();  // (and the routed queries', which only several ranks run)
   if (cfg->n_ranks > 1 && cfg->comm_id) {
     ncclUniqueId id;
     memcpy(&id, cfg->comm_id, sizeof id);
@@ -3461,6 +3485,7 @@ void mhmkc_destroy(mhmkc_t h) {
                     &h->d_fq_bytes, &h->d_fq_offs,    &h->d_fq_err};
   for (DevBuf *b : bufs) b->release();
   h->drop_query();
+  h->drop_route();
   DevBuf *cbufs[] = {&h->d_ctg_bytes, &h->d_ctg_offs, &h->d_ctg_win,   &h->d_ctg_depth, &h->d_ctg_scratch,
                      &h->d_ctg_state, &h->d_ctg_bucket, &h->d_ctg_done, &h->d_ctg_keys[0], &h->d_ctg_keys[1],
                      &h->d_ctg_keys[2], &h->d_ctg_keys[3]};
@@ -5056,6 +5081,377 @@ int mhmkc_uutigs_ranks_info(mhmkc_t h, mhmkc_uutig_ranks_info *info) {
   return MHMKC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// queries routed to the owner rank (kcount_route.hip): get_kmer_target_rank + rpc
+// (src/dbjg_traversal.cpp:228-236,260-274, src/kcount/kmer_dht.cpp:193-219)
+
+static uint64_t route_chunk() {
+  uint64_t c = 1ull << 22;
+  if (const char *env = getenv("MHMKC_ROUTE_CHUNK")) c = strtoull(env, nullptr, 10);
+  return std::max<uint64_t>(1, std::min<uint64_t>(c, 1ull << 30));
+}
+
+// The rounds of one collective call. links: the entries are this rank's 2 * n_out link entries and the results go to
+// d_rlinks; else the n keys at d_keys, the results to the five output arrays (any may be null). Collectives, in this order
+// on every rank: the sizes (entries, rows, rounds, failed); per round the owners' counts with the failed flag, the
+// allocation verdicts, the queries, the replies; the status. Every decision that leads into a collective or past one is
+// taken from gathered values. A rank that fails alone (lrc) keeps entering the round's collectives with the sizes it
+// announced and reports at the next flag. ev: six events, the marks of a round.
+int mhmkc::route_run(bool links, const uint64_t *d_keys, uint64_t n, int canonicalize, uint8_t *d_ranks, uint32_t *d_rows,
+                     uint16_t *d_counts, char *d_left, char *d_right, int pre_rc, hipEvent_t *ev) {
+  const int g = G(), me = cfg.rank;
+  const uint64_t chunk = route_chunk();
+  const uint64_t entries = links ? 2 * n_out : n;
+  int lrc = pre_rc, rc;
+  std::string lerr = err;
+  auto lfail = [&](int r) {
+    if (r && !lrc) {
+      lrc = r;
+      lerr = err;
+    }
+  };
+  auto own = [&]() {
+    err = lerr;
+    return lrc;
+  };
+  hipError_t e;
+  rinfo.chunk = chunk;
+  rinfo.entries = entries;
+
+  // this rank alone, before the first collective: its index and the asking side's scratch
+  if (!lrc && n_out) lfail(query_index());
+  const uint64_t cm = std::min(chunk, entries);
+  const size_t send_b = align_up(cm * 8 * (size_t)nl, 256), reply_b = align_up(cm * 8, 256), pos_b = align_up(cm * 4, 256),
+               dest_b = align_up(cm, 256), tab_b = align_up(8 * 3 * (size_t)g, 256);
+  if (!lrc && (e = grow(d_rt_ask, send_b + reply_b + pos_b + dest_b + tab_b)) != hipSuccess)
+    lfail(e == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "routed queries: scratch for %llu queries", (unsigned long long)cm)
+                                   : hip_fail(e, "routed queries: scratch"));
+  char *ab = d_rt_ask.as<char>();
+  uint64_t *send = (uint64_t *)ab;
+  unsigned long long *reply = (unsigned long long *)(ab + send_b);
+  uint32_t *pos = (uint32_t *)(ab + send_b + reply_b);
+  uint8_t *dest = (uint8_t *)(ab + send_b + reply_b + pos_b);
+  unsigned long long *d_hist = (unsigned long long *)(ab + send_b + reply_b + pos_b + dest_b), *d_cursor = d_hist + g,
+                     *d_nrows = d_hist + 2 * g;
+
+  // the sizes
+  const uint64_t mine[4] = {entries, n_out, (entries + chunk - 1) / chunk, (uint64_t)(lrc ? 1 : 0)};
+  std::vector<uint64_t> all(4 * (size_t)g, 0);
+  if ((rc = allgather_host(mine, all.data(), 32))) return rc;
+  if (lrc) return own();
+  uint64_t rounds = 0;
+  std::vector<unsigned long long> nrows((size_t)g, 0);
+  for (int r = 0; r < g; r++) {
+    if (all[4 * (size_t)r + 3])
+      return fail(MHMKC_ETRANSPORT, "routed queries: rank %d failed (its mhmkc_last_error says why)", r);
+    nrows[(size_t)r] = all[4 * (size_t)r + 1];
+    rounds = std::max(rounds, all[4 * (size_t)r + 2]);
+  }
+  if (all[4 * (size_t)me] != entries || nrows[(size_t)me] != n_out)  // (reported at the next flag, like any local failure)
+    lfail(fail(MHMKC_ETRANSPORT, "routed queries: the gathered sizes do not hold this rank's"));
+  if ((e = hipMemcpyAsync(d_nrows, nrows.data(), 8 * (size_t)g, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess)
+    lfail(hip_fail(e, "routed queries: row counts"));
+  rinfo.rounds = rounds;
+
+  const size_t qb = 8 * (size_t)nl;
+  const mhm::QueryIndex ix = n_out ? qidx : mhm::QueryIndex{};
+  std::vector<uint64_t> hist((size_t)g + 1), start((size_t)g), roff((size_t)g), mat((size_t)g * (g + 1));
+  std::vector<Xfer> snd, rcv;
+  for (uint64_t t = 0; t < rounds; t++) {
+    const uint64_t i0 = std::min(entries, t * chunk), m = std::min(chunk, entries - i0);
+    const mhm::RouteSource src{links ? 1 : 0, links ? nullptr : d_keys + i0 * (uint64_t)nlo, canonicalize, out_rows(), n_out, i0};
+    // 1. the owners of this rank's queries
+    (void)hipEventRecord(ev[0], stream);
+    std::fill(hist.begin(), hist.end(), 0);
+    if (!lrc && m) {
+      if ((e = hipMemsetAsync(d_hist, 0, 8 * (size_t)g, stream)) != hipSuccess ||
+          (e = mhm::launch_route(src, m, k, nl, nlo, mlen, g, dest, d_hist, stream)) != hipSuccess ||
+          (e = hipMemcpyAsync(hist.data(), d_hist, 8 * (size_t)g, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+          (e = hipStreamSynchronize(stream)) != hipSuccess) {
+        lfail(hip_fail(e, "routed queries: owners"));
+        std::fill(hist.begin(), hist.end(), 0);
+      }
+      uint64_t counted = 0;
+      for (int r = 0; r < g; r++) counted += hist[(size_t)r];
+      if (counted > m) {  // (before the counts are announced: the layout holds m places)
+        lfail(fail(MHMKC_EHIP, "routed queries: %llu owners for %llu queries", (unsigned long long)counted,
+                   (unsigned long long)m));
+        std::fill(hist.begin(), hist.end(), 0);
+      }
+    }
+    (void)hipEventRecord(ev[1], stream);
+    // 2. who asks whom how much, and who has failed
+    hist[(size_t)g] = lrc ? 1 : 0;
+    if ((rc = allgather_host(hist.data(), mat.data(), 8 * ((size_t)g + 1)))) return rc;
+    auto M = [&](int from, int to) { return mat[(size_t)from * (g + 1) + to]; };
+    for (int r = 0; r < g; r++)
+      if (M(r, g)) return lrc ? own() : fail(MHMKC_ETRANSPORT, "routed queries: rank %d failed (its mhmkc_last_error says why)", r);
+    uint64_t total = 0, R = 0;
+    bool remote = false;  // (the same on every rank: a round in which every query is local moves nothing)
+    for (int a = 0; a < g; a++)
+      for (int b2 = 0; b2 < g; b2++) remote |= a != b2 && M(a, b2) != 0;
+    for (int r = 0; r < g; r++) {
+      if (M(me, r) != hist[(size_t)r])  // (the rank goes on with the sizes it announced and reports at the next flag)
+        lfail(fail(MHMKC_ETRANSPORT, "routed queries: the gathered counts do not hold this rank's"));
+      start[(size_t)r] = total;
+      total += hist[(size_t)r];
+      roff[(size_t)r] = R;
+      if (r != me) R += M(r, me);
+    }
+    // 3. and 4. room for the received queries and their replies, on every rank or the round does not start
+    const size_t rk_b = align_up(R * qb, 256);
+    uint64_t ok = 1;
+    if (R && (e = grow(d_rt_recv, rk_b + R * 8)) != hipSuccess) {
+      (void)hipGetLastError();
+      ok = 0;
+    }
+    std::vector<uint64_t> oks((size_t)g, 0);
+    if ((rc = allgather_host(&ok, oks.data(), 8))) return rc;
+    for (int r = 0; r < g; r++)
+      if (!oks[(size_t)r])
+        return fail(MHMKC_ENOMEM, "routed queries: rank %d could not allocate for the queries it receives", r);
+    uint64_t *recvk = d_rt_recv.as<uint64_t>();
+    unsigned long long *rreply = (unsigned long long *)(d_rt_recv.as<char>() + rk_b);
+    rinfo.scratch_bytes = std::max<uint64_t>(rinfo.scratch_bytes, d_rt_ask.cap + d_rt_recv.cap);
+    // 5. the queries, grouped by owner, to their owners
+    if (!lrc && m &&
+        ((e = hipMemcpyAsync(d_cursor, start.data(), 8 * (size_t)g, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+         (e = mhm::launch_route_pack(src, m, k, nl, nlo, dest, g, d_cursor, send, pos, stream)) != hipSuccess))
+      lfail(hip_fail(e, "routed queries: pack"));
+    snd.clear();
+    rcv.clear();
+    for (int p = 0; p < g; p++) {
+      if (p == me) continue;
+      if (hist[(size_t)p]) snd.push_back({p, send + start[(size_t)p] * nl, hist[(size_t)p] * qb});
+      if (M(p, me)) rcv.push_back({p, recvk + roff[(size_t)p] * nl, M(p, me) * qb});
+    }
+    const uint64_t sent0 = st.bytes_sent, recv0 = st.bytes_recv;  // (bytes_* count the record exchange only)
+    rc = remote ? move(snd, rcv) : MHMKC_OK;
+    (void)hipEventRecord(ev[2], stream);
+    // 6. the answers: this rank's own queries in place, the received ones from the rank's index
+    if (!rc && !lrc &&
+        ((e = mhm::launch_route_answer(send + start[(size_t)me] * nl, hist[(size_t)me], k, nl, nlo, ix, out_rows(),
+                                       reply + start[(size_t)me], stream)) != hipSuccess ||
+         (e = mhm::launch_route_answer(recvk, R, k, nl, nlo, ix, out_rows(), rreply, stream)) != hipSuccess))
+      lfail(hip_fail(e, "routed queries: answers"));
+    (void)hipEventRecord(ev[3], stream);
+    // 7. the replies back, along the transposed sizes
+    if (!rc) {
+      snd.clear();
+      rcv.clear();
+      for (int p = 0; p < g; p++) {
+        if (p == me) continue;
+        if (M(p, me)) snd.push_back({p, rreply + roff[(size_t)p], M(p, me) * 8});
+        if (hist[(size_t)p]) rcv.push_back({p, reply + start[(size_t)p], hist[(size_t)p] * 8});
+      }
+      if (remote) rc = move(snd, rcv);
+    }
+    st.bytes_sent = sent0;
+    st.bytes_recv = recv0;
+    if (rc) return rc;
+    (void)hipEventRecord(ev[4], stream);
+    // 8. every query's reply from its place
+    if (!lrc && m) {
+      if (links)
+        e = mhm::launch_route_verdict(src, m, k, nl, nlo, reply, pos, dest, total, g, d_nrows, rl_rank(), rl_row(),
+                                      rl_status(), stream);
+      else
+        e = mhm::launch_route_unpack(reply, pos, dest, m, total, g, d_nrows, d_ranks ? d_ranks + i0 : nullptr,
+                                     d_rows ? d_rows + i0 : nullptr, d_counts ? d_counts + i0 : nullptr,
+                                     d_left ? d_left + i0 : nullptr, d_right ? d_right + i0 : nullptr, stream);
+      if (e != hipSuccess) lfail(hip_fail(e, "routed queries: unpack"));
+    }
+    (void)hipEventRecord(ev[5], stream);
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) lfail(hip_fail(e, "routed queries"));
+    for (int i = 0; i < MHMKC_ROUTE_STAGES; i++) {
+      float f = 0;
+      if (hipEventElapsedTime(&f, ev[i], ev[i + 1]) == hipSuccess) rinfo.ms_stage[i] += (double)f;
+    }
+    rinfo.queries += total;
+    rinfo.queries_local += hist[(size_t)me];
+    rinfo.queries_sent += total - hist[(size_t)me];
+    rinfo.queries_recv += R;
+    rinfo.bytes_sent += (total - hist[(size_t)me]) * qb + R * 8;
+    rinfo.bytes_recv += R * qb + (total - hist[(size_t)me]) * 8;
+  }
+
+  // the status: a rank that failed in the last round fails every rank
+  const uint64_t bad = lrc ? 1 : 0;
+  std::vector<uint64_t> bads((size_t)g, 0);
+  if ((rc = allgather_host(&bad, bads.data(), 8))) return rc;
+  if (lrc) return own();
+  for (int r = 0; r < g; r++)
+    if (bads[(size_t)r])
+      return fail(MHMKC_ETRANSPORT, "routed queries: rank %d failed (its mhmkc_last_error says why)", r);
+  return MHMKC_OK;
+}
+
+int mhmkc::route_rounds(bool links, const uint64_t *d_keys, uint64_t n, int canonicalize, uint8_t *d_ranks,
+                        uint32_t *d_rows, uint16_t *d_counts, char *d_left, char *d_right, int pre_rc) {
+  const auto t0 = std::chrono::steady_clock::now();
+  rinfo = mhmkc_route_info_t{};
+  hipEvent_t ev[MHMKC_ROUTE_STAGES + 1] = {};
+  const std::string perr = err;
+  for (hipEvent_t &x : ev)
+    if (!pre_rc && hipEventCreate(&x) != hipSuccess) pre_rc = hip_fail(hipGetLastError(), "routed queries: events");
+  if (pre_rc && err.empty()) err = perr;
+  const int rc = route_run(links, d_keys, n, canonicalize, d_ranks, d_rows, d_counts, d_left, d_right, pre_rc, ev);
+  (void)hipStreamSynchronize(stream);
+  for (hipEvent_t x : ev)
+    if (x) (void)hipEventDestroy(x);
+  d_rt_ask.release();
+  d_rt_recv.release();
+  rinfo.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return rc;
+}
+
+int mhmkc::dbjg_links_ranks() {
+  if (rlinks_ready) return MHMKC_OK;
+  int pre = MHMKC_OK;
+  if (n_out >= 0xffffffffull) pre = fail(MHMKC_EUNSUPPORTED, "table queries: at most 2^32-2 rows");
+  hipError_t e;
+  if (!pre && n_out && (e = grow(d_rlinks, align_up(n_out * 8, 256) + 2 * align_up(n_out * 2, 256))) != hipSuccess)
+    pre = e == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "dbjg links: %llu rows", (unsigned long long)n_out)
+                                   : hip_fail(e, "dbjg links");
+  const int rc = route_rounds(true, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, pre);
+  if (rc) {
+    d_rlinks.release();
+  } else {
+    rlinks_ready = true;
+    rinfo.kept_bytes = d_rlinks.cap;
+  }
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return rc;
+}
+
+// Both refusals of the routed calls, before any collective: the owner, then the state.
+static int route_need(mhmkc_t h, const char *what) {
+  if (h->cfg.output_owner != MHMKC_OWNER_MINIMIZER)
+    return h->fail(MHMKC_EUNSUPPORTED, "%s: MHMKC_OWNER_MINIMIZER handles only", what);
+  if (h->cfg.n_ranks > 255) return h->fail(MHMKC_EUNSUPPORTED, "%s: at most 255 ranks", what);
+  if (!h->finished) return h->fail(MHMKC_ESTATE, "%s before finish", what);
+  return MHMKC_OK;
+}
+
+int mhmkc_lookup_ranks_device(mhmkc_t h, const uint64_t *d_keys, uint64_t n, int canonicalize, uint8_t *d_ranks,
+                              uint32_t *d_rows, uint16_t *d_counts, char *d_left, char *d_right) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks <= 1) {
+    int rc = mhmkc_lookup_device(h, d_keys, n, canonicalize, d_rows, d_counts, d_left, d_right);
+    if (rc) return rc;
+    hipError_t e = d_ranks && n ? hipMemsetAsync(d_ranks, 0, n, h->stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "lookup_ranks");
+  }
+  int rc = route_need(h, "lookup_ranks");
+  if (rc) return rc;
+  // (a bad argument on one rank: the rank still enters the collective and fails it for all)
+  const int pre = n && !d_keys ? h->fail(MHMKC_EINVAL, "null key buffer") : MHMKC_OK;
+  return h->route_rounds(false, d_keys, pre ? 0 : n, canonicalize != 0, d_ranks, d_rows, d_counts, d_left, d_right, pre);
+}
+
+int mhmkc_lookup_ranks(mhmkc_t h, const uint64_t *keys, uint64_t n, int canonicalize, uint8_t *ranks, uint32_t *rows,
+                       uint16_t *counts, char *left, char *right) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks <= 1) {
+    int rc = mhmkc_lookup(h, keys, n, canonicalize, rows, counts, left, right);
+    if (!rc && ranks && n) memset(ranks, 0, n);
+    return rc;
+  }
+  int rc = route_need(h, "lookup_ranks");
+  if (rc) return rc;
+  // the whole batch staged on the device: keys in, the five outputs back
+  int pre = n && !keys ? h->fail(MHMKC_EINVAL, "null key buffer") : MHMKC_OK;
+  const size_t kb = align_up(n * 8 * (size_t)h->nlo, 256), rb = align_up(n * 4, 256), cb = align_up(n * 2, 256),
+               lb = align_up(n, 256);
+  hipError_t e = hipSuccess;
+  if (!pre && n && (e = h->grow(h->d_qstage, kb + rb + cb + 3 * lb)) != hipSuccess)
+    pre = e == hipErrorOutOfMemory ? h->fail(MHMKC_ENOMEM, "lookup_ranks: staging for %llu keys", (unsigned long long)n)
+                                   : h->hip_fail(e, "lookup_ranks staging");
+  char *base = h->d_qstage.as<char>();
+  uint64_t *dk = (uint64_t *)base;
+  uint32_t *dr = (uint32_t *)(base + kb);
+  uint16_t *dc = (uint16_t *)(base + kb + rb);
+  char *dl = base + kb + rb + cb, *drt = dl + lb;
+  uint8_t *dq = (uint8_t *)(drt + lb);
+  if (!pre && n && (e = hipMemcpyAsync(dk, keys, n * 8 * (size_t)h->nlo, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+    pre = h->hip_fail(e, "lookup_ranks H2D");
+  rc = h->route_rounds(false, dk, pre ? 0 : n, canonicalize != 0, ranks ? dq : nullptr, rows ? dr : nullptr,
+                       counts ? dc : nullptr, left ? dl : nullptr, right ? drt : nullptr, pre);
+  if (rc || !n) return rc;
+  if (ranks) e = h->d2h(ranks, dq, n);
+  if (e == hipSuccess && rows) e = h->d2h(rows, dr, n * 4);
+  if (e == hipSuccess && counts) e = h->d2h(counts, dc, n * 2);
+  if (e == hipSuccess && left) e = h->d2h(left, dl, n);
+  if (e == hipSuccess && right) e = h->d2h(right, drt, n);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "lookup_ranks D2H");
+}
+
+int mhmkc_dbjg_links_ranks(mhmkc_t h) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks <= 1) {  // one rank: mhmkc_dbjg_links, and rank 0 wherever it names a row (d_rlinks: the ranks alone)
+    if (!h->finished) return h->fail(MHMKC_ESTATE, "dbjg links before finish");
+    int rc = h->dbjg_links();
+    if (rc || h->rlinks_ready) return rc;
+    const uint64_t n = h->n_out;
+    hipError_t e;
+    if (n && ((e = h->grow(h->d_rlinks, 2 * n + 64)) != hipSuccess ||
+              (e = mhm::launch_route_rank0(h->d_links.as<uint32_t>(), 2 * n, h->d_rlinks.as<uint8_t>(), h->stream)) !=
+                  hipSuccess)) {
+      h->d_rlinks.release();
+      return h->hip_fail(e, "dbjg links");
+    }
+    h->rinfo = mhmkc_route_info_t{};
+    h->rinfo.entries = 2 * n;
+    h->rinfo.kept_bytes = h->d_links.cap + h->d_rlinks.cap;
+    h->rlinks_ready = true;
+    h->st.device_bytes = g_dev_live.load();
+    h->st.device_bytes_peak = g_dev_peak.load();
+    return MHMKC_OK;
+  }
+  int rc = route_need(h, "dbjg_links_ranks");
+  if (rc) return rc;
+  return h->dbjg_links_ranks();
+}
+
+int mhmkc_dbjg_links_ranks_device(mhmkc_t h, const uint8_t **d_next_rank, const uint32_t **d_next_row,
+                                  const uint8_t **d_status) {
+  int rc = mhmkc_dbjg_links_ranks(h);
+  if (rc) return rc;
+  const uint64_t n = h->n_out;
+  const bool one = h->cfg.n_ranks <= 1;
+  if (d_next_rank) *d_next_rank = !n ? nullptr : one ? h->d_rlinks.as<uint8_t>() : h->rl_rank();
+  if (d_next_row) *d_next_row = !n ? nullptr : one ? h->d_links.as<uint32_t>() : h->rl_row();
+  if (d_status) *d_status = !n ? nullptr : one ? (const uint8_t *)(h->d_links.as<uint32_t>() + 2 * n) : h->rl_status();
+  return MHMKC_OK;
+}
+
+int mhmkc_dbjg_links_ranks_fetch(mhmkc_t h, uint8_t *next_rank, uint32_t *next_row, uint8_t *status) {
+  const uint8_t *dk = nullptr, *ds = nullptr;
+  const uint32_t *dr = nullptr;
+  int rc = mhmkc_dbjg_links_ranks_device(h, &dk, &dr, &ds);
+  if (rc) return rc;
+  const uint64_t n = h->n_out;
+  if (!n) return MHMKC_OK;
+  hipError_t e = hipSuccess;
+  if (next_rank) e = h->d2h(next_rank, dk, 2 * n);
+  if (e == hipSuccess && next_row) e = h->d2h(next_row, dr, 2 * n * 4);
+  if (e == hipSuccess && status) e = h->d2h(status, ds, 2 * n);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "dbjg links D2H");
+}
+
+int mhmkc_route_info(mhmkc_t h, mhmkc_route_info_t *info) {
+  if (!h || !info) return MHMKC_EINVAL;
+  *info = h->rinfo;
+  return MHMKC_OK;
+}
+
 int mhmkc_ctgs_ranks_info(mhmkc_t h, mhmkc_ctg_ranks_info *info) {
   if (!h || !info) return MHMKC_EINVAL;
   *info = h->cinfo;
@@ -5103,8 +5499,10 @@ int mhmkc_reset(mhmkc_t h) {
   h->partial = false;
   h->n_out = 0;
   h->ord_ready = false;
-  const bool had_query = h->d_qidx.p || h->d_links.p || h->d_qstage.p || h->d_uctg.p || h->d_urows.p || h->d_useq.p;
+  const bool had_query =
+      h->d_qidx.p || h->d_links.p || h->d_qstage.p || h->d_uctg.p || h->d_urows.p || h->d_useq.p || h->d_rlinks.p;
   h->drop_query();
+  h->drop_route();
   memset(&h->st, 0, sizeof h->st);
   if (had_query || had_pc) {  // (these buffers were counted into the finished round's device_bytes: report what is left)
     h->st.device_bytes = g_dev_live.load();

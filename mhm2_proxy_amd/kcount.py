@@ -636,6 +636,73 @@ class KmerCounter:
         self._check(N.lib().mhmkc_uutigs_ranks_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    # -- queries answered by the owner rank (mhmkc_lookup_ranks, mhmkc_dbjg_links_ranks)
+    def lookup_ranks(self, keys, canonicalize: bool = False):
+        """lookup() for k-mers that may live on any rank (mhmkc_lookup_ranks; get_kmer_target_rank + the rpc of
+        src/dbjg_traversal.cpp:228-236): collective over the ranks of a finished MHMKC_OWNER_MINIMIZER counter, every rank
+        with its own batch (an empty one too). Returns numpy arrays (ranks uint8, rows, counts, left, right): ranks[i] is
+        the key's owner, always set; rows[i] the row of that rank's fetch() or MHMKC_NO_ROW, the rest as lookup()."""
+        kk = self._query_keys(keys)
+        n = kk.shape[0]
+        ranks = np.empty(n, dtype=np.uint8)
+        rows = np.empty(n, dtype=np.uint32)
+        counts = np.empty(n, dtype=np.uint16)
+        left = np.empty(n, dtype=np.uint8)
+        right = np.empty(n, dtype=np.uint8)
+        self._check(N.lib().mhmkc_lookup_ranks(self._h, kk.ctypes.data if n else None, n, int(bool(canonicalize)),
+                                               ranks.ctypes.data, rows.ctypes.data, counts.ctypes.data, left.ctypes.data,
+                                               right.ctypes.data))
+        return ranks, rows, counts, left, right
+
+    def lookup_ranks_tensors(self, keys_t, canonicalize: bool = False):
+        """lookup_ranks() for keys already in HBM (mhmkc_lookup_ranks_device), following lookup_tensors: torch tensors
+        (ranks uint8, rows int32 holding the uint32 bits, counts int16 holding the uint16 bits, left, right uint8). The
+        call is a collective and returns with the tensors complete."""
+        import torch
+
+        if keys_t.dtype not in (torch.uint64, torch.int64):
+            raise ValueError("keys_t must be a uint64 or int64 tensor")
+        if not keys_t.is_contiguous() or keys_t.numel() % self.n_longs:
+            raise ValueError("keys_t must be contiguous with n * n_longs words")
+        n = keys_t.numel() // self.n_longs
+        dev = keys_t.device
+        ranks = torch.empty(n, dtype=torch.uint8, device=dev)
+        rows = torch.empty(n, dtype=torch.int32, device=dev)
+        counts = torch.empty(n, dtype=torch.int16, device=dev)
+        left = torch.empty(n, dtype=torch.uint8, device=dev)
+        right = torch.empty(n, dtype=torch.uint8, device=dev)
+        self._after_torch(keys_t)
+        self._check(N.lib().mhmkc_lookup_ranks_device(self._h, keys_t.data_ptr() if n else None, n,
+                                                      int(bool(canonicalize)), ranks.data_ptr(), rows.data_ptr(),
+                                                      counts.data_ptr(), left.data_ptr(), right.data_ptr()))
+        return ranks, rows, counts, left, right
+
+    def dbjg_links_ranks(self):
+        """dbjg_links() with every neighbour looked up on its owner rank (mhmkc_dbjg_links_ranks; get_next_step at
+        rank_n() > 1): numpy arrays next_rank uint8 [2, n_out] (MHMKC_NO_RANK: none), next_row uint32 [2, n_out] (the
+        row on that rank, MHMKC_NO_ROW: none) and status [2, n_out]. The first call after a finish is a collective; the
+        arrays are kept on the device, so a later call runs none."""
+        n = self.n_out or 0  # (before finish the library refuses the call)
+        next_rank = np.empty((2, n), dtype=np.uint8)
+        next_row = np.empty((2, n), dtype=np.uint32)
+        status = np.empty((2, n), dtype=np.uint8)
+        self._check(N.lib().mhmkc_dbjg_links_ranks_fetch(self._h, next_rank.ctypes.data, next_row.ctypes.data,
+                                                         status.ctypes.data))
+        return next_rank, next_row, status
+
+    def dbjg_links_ranks_device(self) -> dict:
+        """Device pointers of the kept arrays (mhmkc_dbjg_links_ranks_device), valid until the next reset / finish."""
+        pk, pr, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(N.lib().mhmkc_dbjg_links_ranks_device(self._h, C.byref(pk), C.byref(pr), C.byref(ps)))
+        return {"next_rank": pk.value, "next_row": pr.value, "status": ps.value, "n_out": self.n_out}
+
+    def route_info(self) -> dict:
+        """Rounds, queries and bytes between the ranks, stage times and memory of the last lookup_ranks /
+        dbjg_links_ranks collective on this counter (mhmkc_route_info)."""
+        info = N.MhmkcRouteInfo()
+        self._check(N.lib().mhmkc_route_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def stats(self) -> dict:
         s = N.MhmkcStats()
         self._check(N.lib().mhmkc_get_stats(self._h, C.byref(s)))
