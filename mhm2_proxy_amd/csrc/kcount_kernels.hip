@@ -1767,13 +1767,26 @@ __device__ __forceinline__ int cmp_group(uint32_t key, int kshl, uint32_t ng) {
   return (int)(__umul24((key << kshl) >> 16, ng) >> 16);
 }
 
+// MHMKC_ADDLUT: how a cold sweep's left add finds its word among the table's five contiguous counter planes (lds_add_nr).
+//   0  a compare, a multiply and two selects (round 1);
+//   1  a nibble table of plane numbers counted from the count word (round 7);
+//   2  (round 9) the planes ordered left A|C, left G|T, count, right A|C, right G|T: the left add's plane is l >> 1 for
+//      l = 0 .. 4 (4: a neighbour that is no countable base, counted in the count word), one bit-field extract of
+//      the ext code. The order is spelled here alone: every reader goes through cnt() and ext().
+#ifndef MHMKC_ADDLUT
+#define MHMKC_ADDLUT 2
+#endif
 template <typename K>  // key word type: uint64_t, or uint32_t for compact records
 struct CountLds {
   K *keys;         // [NL][cap]
-  uint32_t *cnt;   // [cap]
-  uint32_t *ext;   // [4][cap]: (A|C<<16, G|T<<16) left, then right
+  uint32_t *ctr;   // [5][cap]: the count plane and the four extension planes, in the order of plane_of
   int cap;         // multiple of 4: slots are probed in groups of 4
   uint32_t *clog;  // the sweep's clamp log (ext_clamp), or null when no threshold can pass the clamp's target
+  static constexpr uint32_t CNT_PLANE = MHMKC_ADDLUT == 2 ? 2u : 0u;
+  // extension plane i: (A|C<<16, G|T<<16) left, then right
+  static constexpr __device__ uint32_t plane_of(uint32_t i) { return MHMKC_ADDLUT == 2 ? (i < 2u ? i : i + 1u) : i + 1u; }
+  __device__ __forceinline__ uint32_t *cnt() const { return ctr + CNT_PLANE * (uint32_t)cap; }               // [cap]
+  __device__ __forceinline__ uint32_t *ext(uint32_t i) const { return ctr + plane_of(i) * (uint32_t)cap; }  // [cap]
 };
 
 // An LDS fetch-add whose result is used later (k_count's dynamic slot counter, read at the end of the round): the
@@ -1865,6 +1878,11 @@ constexpr int G_FULL = -8, G_BUSY = -9;
 // MHMKC_MISSQ1 (round 8): the compact cold phase A checks the miss queue's room once per round, not once per record.
 #ifndef MHMKC_MISSQ1
 #define MHMKC_MISSQ1 0
+#endif
+// MHMKC_VALIDU (round 9, needs MHMKC_RESOLVE): wave-uniform validity in the compact cold phase A of dynamic sweeps (see
+// the round loop): claims, adds and miss masks of a whole slot carry no per-record validity test.
+#ifndef MHMKC_VALIDU
+#define MHMKC_VALIDU 1
 #endif
 __device__ __forceinline__ int verdict_code(uint32_t m, int g) {
   return verdict_found(m) ? 4 * g + (int)m : verdict_empty(m) ? 3 - (int)m : G_FULL;
@@ -1989,10 +2007,10 @@ __device__ __forceinline__ int claim_home(const CountLds<K> &t, const uint64_t *
 // is returned for the saturation check (lds_clamp).
 template <typename K>
 __device__ __forceinline__ uint32_t lds_add(const CountLds<K> &t, int slot, uint32_t e) {
-  const uint32_t old = atomicAdd(&t.cnt[slot], 1u);
+  const uint32_t old = atomicAdd(&t.cnt()[slot], 1u);
   const int l = (int)((e >> 3) & 7u), r = (int)(e & 7u);
-  if (l < 4) atomicAdd(&t.ext[(l >> 1) * t.cap + slot], (l & 1) ? 0x10000u : 1u);
-  if (r < 4) atomicAdd(&t.ext[(2 + (r >> 1)) * t.cap + slot], (r & 1) ? 0x10000u : 1u);
+  if (l < 4) atomicAdd(&t.ext(l >> 1)[slot], (l & 1) ? 0x10000u : 1u);
+  if (r < 4) atomicAdd(&t.ext(2 + (r >> 1))[slot], (r & 1) ? 0x10000u : 1u);
   return old;
 }
 
@@ -2003,37 +2021,78 @@ __device__ __forceinline__ uint32_t lds_add(const CountLds<K> &t, int slot, uint
 // the wave. slot_count() reads it back; ctg_apply stores an explicit count as 0x80000000 | count.
 // (Three adds, count and both extensions: 8.24 -> 8.32 ms in round 1; branch-free adds of 0 by every lane
 // that has nothing to count: 4.85 -> 5.04 ms in round 3.)
-// MHMKC_ADDLUT (round 7): the left add's word from a nibble table of plane numbers counted from the count word (cnt
-// and the four extension planes are contiguous: 0 the count word for left-none, 1 for A/C, 2 for G/T), one
-// shift-and-mask and one 24-bit multiply-add instead of a compare, a multiply and two selects; the addend is a shift
-// of 1; a right-none is skipped (the compiler branched around the right add's address anyway).
-#ifndef MHMKC_ADDLUT
-#define MHMKC_ADDLUT 1
+// MHMKC_ADDLUT (see CountLds) = 1, round 7: the left add's word from a nibble table of plane numbers counted from the
+// count word (0 the count word for left-none, 1 for A/C, 2 for G/T), one shift-and-mask and one 24-bit multiply-add
+// instead of a compare, a multiply and two selects; the addend is a shift of 1; a right-none is skipped (the compiler
+// branched around the right add's address anyway). = 2, round 9: the plane is bits 4-5 of the ext code (l <= 4).
+// The left add's plane among the five counter planes (l = 0 .. 4, EXT_NONE = 4 the count word)
+__device__ __forceinline__ uint32_t cold_left_plane(uint32_t e) {
+#if MHMKC_ADDLUT == 2
+  static_assert(EXT_NONE == 4, "left-none must select the count plane");
+  return (e >> 4) & 3u;
+#else
+  return (0x2211u >> ((e >> 1) & 0x1cu)) & 3u;
 #endif
+}
 template <typename K>
 __device__ __forceinline__ void lds_add_nr(const CountLds<K> &t, int slot, uint32_t e, uint32_t *dummy) {
 #if MHMKC_ADDLUT
-  const uint32_t pl = (0x2211u >> ((e >> 1) & 0x1cu)) & 3u, r = e & 7u;
-  atomicAdd(&t.cnt[pl * (uint32_t)t.cap + (uint32_t)slot], 1u << ((e & 8u) << 1));
-  if (r < 4u) atomicAdd(&t.cnt[(3u + (r >> 1)) * (uint32_t)t.cap + (uint32_t)slot], 1u << ((e & 1u) << 4));
+  const uint32_t pl = cold_left_plane(e), r = e & 7u;
+  atomicAdd(&t.ctr[pl * (uint32_t)t.cap + (uint32_t)slot], 1u << ((e & 8u) << 1));
+  if (r < 4u) atomicAdd(&t.ctr[(3u + (r >> 1)) * (uint32_t)t.cap + (uint32_t)slot], 1u << ((e & 1u) << 4));
   (void)dummy;
 #else
   const uint32_t l = (e >> 3) & 7u, r = e & 7u;
-  uint32_t *lw = l < 4u ? &t.ext[(l >> 1) * t.cap + slot] : &t.cnt[slot];
+  uint32_t *lw = l < 4u ? &t.ext(l >> 1)[slot] : &t.cnt()[slot];
   atomicAdd(lw, (l & 1u) ? 0x10000u : 1u);
-  uint32_t *rw = r < 4u ? &t.ext[(2 + (r >> 1)) * t.cap + slot] : dummy;
+  uint32_t *rw = r < 4u ? &t.ext(2 + (r >> 1))[slot] : dummy;
   atomicAdd(rw, (r & 1u) ? 0x10000u : 1u);
 #endif
 }
+// MHMKC_ADD0 (round 9, needs MHMKC_ADDLUT): the add pair of the compact cold phase A without a conditional region.
+// Every lane issues both adds; a lane with nothing to count (a miss, an invalid record, a right-none) adds 0, to a
+// word of its own home group (never one shared dummy word: round 3's zeros all met on one address): the left word
+// its ext code selects, or the slot's count word. One select on each addend and one on the right plane stand for two
+// exec regions (saveexec, skip branch, restore). Built and off: alone it left the count where it was (C2 k = 21:
+// 3.98-4.02 -> 3.92-4.07 ms).
+#ifndef MHMKC_ADD0
+#define MHMKC_ADD0 0
+#endif
+template <typename K>
+__device__ __forceinline__ void lds_add_nr0(const CountLds<K> &t, int slot, uint32_t e, bool add) {
+  static_assert(MHMKC_ADDLUT != 0 || !MHMKC_ADD0, "MHMKC_ADD0 takes its planes from MHMKC_ADDLUT's arithmetic");
+  const uint32_t r = e & 7u;
+  const bool ra = add && r < 4u;
+  // (a lane that adds 0 may carry any e: both plane numbers stay within the five planes, 0 .. 3 and CNT_PLANE .. 4)
+  atomicAdd(&t.ctr[cold_left_plane(e) * (uint32_t)t.cap + (uint32_t)slot], add ? 1u << ((e & 8u) << 1) : 0u);
+  atomicAdd(&t.ctr[(ra ? 3u + (r >> 1) : CountLds<K>::CNT_PLANE) * (uint32_t)t.cap + (uint32_t)slot],
+            ra ? 1u << ((e & 1u) << 4) : 0u);
+}
 
+// MHMKC_FIN1 (round 9): the finalize's pass 1 (see there), and the cold count of a slot as two sum-of-halves
+// instructions (v_sad_u16 against 0 with an accumulator: acc + low half + high half) instead of four masks / shifts and
+// four adds.
+#ifndef MHMKC_FIN1
+#define MHMKC_FIN1 1
+#endif
+// The count of a cold sweep's slot from its count word c and its two left extension words (see lds_add_nr). SAD: the
+// compact instantiation with MHMKC_FIN1 (in the unmixed one-word kernels, which spill as they are, it cost 4-32 more
+// bytes of scratch).
+template <bool SAD>
+__device__ __forceinline__ uint32_t cold_count(uint32_t c, uint32_t e0, uint32_t e1) {
+  uint32_t s;
+  if constexpr (SAD)
+    s = __builtin_amdgcn_sad_u16(e1, 0u, __builtin_amdgcn_sad_u16(e0, 0u, c));
+  else
+    s = c + (e0 & 0xffffu) + (e0 >> 16) + (e1 & 0xffffu) + (e1 >> 16);
+  return (c >> 31) ? c & 0x7fffffffu : s;
+}
 // The count of an occupied slot (see lds_add_nr for the cold-sweep encoding).
 template <typename K>
 __device__ __forceinline__ uint32_t slot_count(const CountLds<K> &t, int slot, bool cold) {
-  const uint32_t c = t.cnt[slot];
+  const uint32_t c = t.cnt()[slot];
   if (!cold) return c;
-  if (c >> 31) return c & 0x7fffffffu;
-  const uint32_t e0 = t.ext[slot], e1 = t.ext[t.cap + slot];
-  return c + (e0 & 0xffffu) + (e0 >> 16) + (e1 & 0xffffu) + (e1 >> 16);
+  return cold_count<MHMKC_FIN1 && sizeof(K) == 4>(c, t.ext(0)[slot], t.ext(1)[slot]);
 }
 
 // Saturation at the decision level: a 16-bit half that reached 0xC000 is CAS-clamped back to 0x8000.
@@ -2107,8 +2166,8 @@ __device__ __forceinline__ void ext_clamp(uint32_t *p, int half, uint32_t *clog,
 template <typename K>
 __device__ __forceinline__ void lds_clamp(const CountLds<K> &t, int slot, uint32_t e) {
   const int l = (int)((e >> 3) & 7u), r = (int)(e & 7u);
-  if (l < 4) ext_clamp(&t.ext[(l >> 1) * t.cap + slot], l & 1, t.clog, (uint32_t)slot << 3 | (uint32_t)l);
-  if (r < 4) ext_clamp(&t.ext[(2 + (r >> 1)) * t.cap + slot], r & 1, t.clog, (uint32_t)slot << 3 | 4u | (uint32_t)r);
+  if (l < 4) ext_clamp(&t.ext(l >> 1)[slot], l & 1, t.clog, (uint32_t)slot << 3 | (uint32_t)l);
+  if (r < 4) ext_clamp(&t.ext(2 + (r >> 1))[slot], r & 1, t.clog, (uint32_t)slot << 3 | 4u | (uint32_t)r);
 }
 
 // Diagnostic phase stamps of k_count (MHMKC_STAMP builds only): wave cycles per phase, summed into
@@ -2217,7 +2276,7 @@ __device__ void ctg_apply(const CountLds<K> &t, const CountParams &p, uint32_t b
       bool keep = false;
       if (rc >= 2) {
         const int thr = dyn_threshold(rc, p.dyn_mult, p.dmin_thres);
-        uint32_t e0 = t.ext[slot], e1 = t.ext[t.cap + slot], e2 = t.ext[2 * t.cap + slot], e3 = t.ext[3 * t.cap + slot];
+        uint32_t e0 = t.ext(0)[slot], e1 = t.ext(1)[slot], e2 = t.ext(2)[slot], e3 = t.ext(3)[slot];
         if (WIDE && n_clog) clog_restore(t.clog, n_clog, (uint32_t)slot, e0, e1, e2, e3);
         const char L = ext_choice(e0 & 0xffffu, e0 >> 16, e1 & 0xffffu, e1 >> 16, thr);
         const char R = ext_choice(e2 & 0xffffu, e2 >> 16, e3 & 0xffffu, e3 >> 16, thr);
@@ -2231,9 +2290,9 @@ __device__ void ctg_apply(const CountLds<K> &t, const CountParams &p, uint32_t b
         uint32_t ew[4] = {0, 0, 0, 0};
         if (l < 4) ew[l >> 1] |= h << ((l & 1u) * 16);
         if (r < 4) ew[2 + (r >> 1)] |= h << ((r & 1u) * 16);
-        t.cnt[slot] = cold ? 0x80000000u | c : c;  // an explicit count (slot_count)
+        t.cnt()[slot] = cold ? 0x80000000u | c : c;  // an explicit count (slot_count)
 #pragma unroll
-        for (int i = 0; i < 4; i++) t.ext[i * t.cap + slot] = ew[i];
+        for (int i = 0; i < 4; i++) t.ext(i)[slot] = ew[i];
       }
       p.ctg_done[q] = 1;
     } else if (last_sweep) {
@@ -2318,11 +2377,10 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
   CountLds<K> t;
   t.cap = p.cap & 0xffff;  // (< 2^16: the compiler then multiplies plane indices by it with v_mul_u32_u24)
   t.keys = (K *)smem;
-  t.cnt = (uint32_t *)(t.keys + NL * t.cap);
-  t.ext = t.cnt + t.cap;
+  t.ctr = (uint32_t *)(t.keys + NL * t.cap);
   t.clog = WIDE ? (uint32_t *)(smem + count_log_offset(NL, RK::C32)) : nullptr;
   // scalars live after the table in the same dynamic region (count_table_bytes adds 256 bytes)
-  unsigned long long *s_u64 = (unsigned long long *)(t.ext + 4 * t.cap);
+  unsigned long long *s_u64 = (unsigned long long *)(t.ctr + 5 * t.cap);
   unsigned long long &s_gbase = s_u64[0];
   unsigned long long *s_red = s_u64 + 1;  // [3]
   unsigned int &s_ovf = *(unsigned int *)(s_u64 + 5);
@@ -2472,7 +2530,7 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
     uint4 *ones = (uint4 *)(t.keys + (NL - 1) * t.cap);
     const int n_ones = t.cap * (int)sizeof(K) / 16;
     for (int i = tid; i < n_ones; i += C_THREADS) ones[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
-    uint4 *zeros = (uint4 *)t.cnt;
+    uint4 *zeros = (uint4 *)t.ctr;
     const int n_zeros = t.cap * 20 / 16;
     for (int i = tid; i < n_zeros; i += C_THREADS) zeros[i] = make_uint4(0, 0, 0, 0);
   };
@@ -2584,9 +2642,15 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
         const uint32_t vend = DYN ? (cend < n ? cend : n) : nw == NONE ? n : nw;
         const uint32_t vrem = (vend > vfirst ? vend : vfirst) - vfirst;
         const uint32_t vstep = RK::C32 ? 1u : (DYN || nw == NONE) ? (uint32_t)C_THREADS : 64u;
+        // MHMKC_VALIDU: the compact cold phase A of a dynamic sweep asks once per round, as a scalar, whether its slot
+        // is whole (every slot of a sweep but the last is); a whole slot runs a copy of phase A without any validity
+        // test, the sweep's last slot the copy that tests record j of a lane by j < vrem. ce[] then holds the ext
+        // codes as loaded: past phase A only missed and deferred records are touched, and those are valid.
+        constexpr bool VU = MHMKC_VALIDU && RK::C32 && COLD && DYN && MHMKC_VERDICT && MHMKC_RESOLVE && GS_SLOTS == 4;
+        const bool whole = VU && __builtin_amdgcn_readfirstlane((int)(cfirst + SLOT <= vend)) != 0;
 #pragma unroll
         for (int j = 0; j < R; j++) {
-          const bool valid = (uint32_t)j * vstep < vrem;
+          const bool valid = VU || (uint32_t)j * vstep < vrem;
 #pragma unroll
           for (int w = 0; w < NL; w++) ck[j][w] = nk[j][w];
           if (PACKED) {
@@ -2635,23 +2699,43 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
             for (int j = 0; j < R; j++)
               vm[j] = group_verdict4((uint32_t)gv[j][0], (uint32_t)gv[j][1], (uint32_t)gv[j][2], (uint32_t)gv[j][3],
                                      (uint32_t)ck[j][0]);
-#pragma unroll
-            for (int j = 0; j < R; j++) {
-              res[j] = 0u;
-              if (ce[j] != NONE && verdict_empty(vm[j]))
-                res[j] = atomicCAS((unsigned int *)&last[GS * g[j] + (int)(vm[j] & 3u)], 0xffffffffu, (uint32_t)ck[j][0]);
-            }
-            if constexpr (MHMKC_RESOLVE) {
-              // three lane masks and one conditional region per record, around its two adds: nothing of the general
-              // path's bookkeeping (old counts, the counted mask, slot marks) exists in a cold sweep
+            // (VU: record j of this lane is valid iff the slot is whole, WH, or j < vrem; otherwise ce[j] says)
+            auto claims = [&](auto whole_tag) {
+              constexpr bool WH = decltype(whole_tag)::value;
 #pragma unroll
               for (int j = 0; j < R; j++) {
+                const bool valid = WH || (VU ? (uint32_t)j < vrem : ce[j] != NONE);
+                res[j] = 0u;
+                if (valid && verdict_empty(vm[j]))
+                  res[j] = atomicCAS((unsigned int *)&last[GS * g[j] + (int)(vm[j] & 3u)], 0xffffffffu, (uint32_t)ck[j][0]);
+              }
+            };
+            // three lane masks and one conditional region per record, around its two adds (MHMKC_ADD0: none): nothing of
+            // the general path's bookkeeping (old counts, the counted mask, slot marks) exists in a cold sweep
+            auto resolve = [&](auto whole_tag) {
+              constexpr bool WH = decltype(whole_tag)::value;
+#pragma unroll
+              for (int j = 0; j < R; j++) {
+                const bool valid = WH || (VU ? (uint32_t)j < vrem : ce[j] != NONE);
                 const bool won = res[j] == 0xffffffffu || res[j] == (uint32_t)ck[j][0];
-                const bool add = ce[j] != NONE && (verdict_found(vm[j]) || (verdict_empty(vm[j]) && won));
-                if (add) lds_add_nr(t, GS * g[j] + (int)(vm[j] & 3u), ce[j], &s_wave[wid]);
-                missm |= (uint32_t)(ce[j] != NONE && !add) << j;
+                const bool add = valid && (verdict_found(vm[j]) || (verdict_empty(vm[j]) && won));
+                if constexpr (MHMKC_ADD0)
+                  lds_add_nr0(t, GS * g[j] + (int)(vm[j] & 3u), ce[j], add);
+                else if (add)
+                  lds_add_nr(t, GS * g[j] + (int)(vm[j] & 3u), ce[j], &s_wave[wid]);
+                missm |= (uint32_t)(valid && !add) << j;
+              }
+            };
+            if constexpr (MHMKC_RESOLVE) {
+              if (whole) {  // (VU only; a scalar branch)
+                claims(std::true_type{});
+                resolve(std::true_type{});
+              } else {
+                claims(std::false_type{});
+                resolve(std::false_type{});
               }
             } else {
+              claims(std::false_type{});
 #pragma unroll
               for (int j = 0; j < R; j++) {
                 int r = verdict_code(vm[j], g[j]);
@@ -2930,20 +3014,22 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
     // entry's depth is >= 1) and a free one count 0, so the counters alone decide, read four slots at a time
     // (one ds_read_b128 per counter plane, consecutive lanes on consecutive quads: no bank conflicts)
     constexpr int QPT = (count_cap(NL, RK::C32) / 4 + C_THREADS - 1) / C_THREADS;
+    constexpr bool FIN1 = MHMKC_FIN1 && RK::C32;
+    // MHMKC_FIN1 (round 9, compact keys): a wave whose 64 quads of iteration j lie past the table leaves pass 1 (1536
+    // quads: the second iteration has work in waves 0-7 only); the cold counts come from cold_count.
 #pragma unroll
     for (int j = 0; j < QPT; j++) {
+      if (FIN1 && 4u * ((uint32_t)wid * 64u + (uint32_t)j * C_THREADS) >= (uint32_t)t.cap) break;
       const int qd = tid + j * C_THREADS;
       uint32_t c[4] = {0, 0, 0, 0};
       if (4 * qd < t.cap) {
-        const uint4 c4 = *(const uint4 *)(t.cnt + 4 * qd);
+        const uint4 c4 = *(const uint4 *)(t.cnt() + 4 * qd);
         c[0] = c4.x, c[1] = c4.y, c[2] = c4.z, c[3] = c4.w;
         if (cold) {  // slot_count's cold encoding, four at a time
-          const uint4 a4 = *(const uint4 *)(t.ext + 4 * qd), b4 = *(const uint4 *)(t.ext + t.cap + 4 * qd);
+          const uint4 a4 = *(const uint4 *)(t.ext(0) + 4 * qd), b4 = *(const uint4 *)(t.ext(1) + 4 * qd);
           const uint32_t a[4] = {a4.x, a4.y, a4.z, a4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
 #pragma unroll
-          for (int i = 0; i < 4; i++)
-            c[i] = (c[i] >> 31) ? c[i] & 0x7fffffffu
-                                : c[i] + (a[i] & 0xffffu) + (a[i] >> 16) + (bb[i] & 0xffffu) + (bb[i] >> 16);
+          for (int i = 0; i < 4; i++) c[i] = cold_count<FIN1>(c[i], a[i], bb[i]);
         }
       }
       // the wave's listed slots take one reservation (ballots + lane prefixes), not one LDS atomic each on the
@@ -3005,16 +3091,14 @@ __global__ __launch_bounds__(C_THREADS, 4) void k_count(CountParams p) {
         sp[j] = (uint32_t)slot;
         uint16_t c16;
         char L, R_;
-        const uint32_t cw = t.cnt[slot];
-        uint32_t e0 = t.ext[slot], e1 = t.ext[t.cap + slot], e2 = t.ext[2 * t.cap + slot], e3 = t.ext[3 * t.cap + slot];
+        const uint32_t cw = t.cnt()[slot];
+        uint32_t e0 = t.ext(0)[slot], e1 = t.ext(1)[slot], e2 = t.ext(2)[slot], e3 = t.ext(3)[slot];
         if (KREG && j < KJ) {  // (with the counters: the same round trip)
 #pragma unroll
           for (int w = 0; w < NL; w++) kreg[j < KJ ? j : 0][w] = t.keys[w * t.cap + slot];
         }
         // slot_count's cold encoding from the words already read
-        const uint32_t c32 = !cold ? cw
-                             : (cw >> 31) ? cw & 0x7fffffffu
-                                          : cw + (e0 & 0xffffu) + (e0 >> 16) + (e1 & 0xffffu) + (e1 >> 16);
+        const uint32_t c32 = !cold ? cw : cold_count<FIN1>(cw, e0, e1);
         if (WIDE && n_clog) clog_restore(t.clog, n_clog, (uint32_t)slot, e0, e1, e2, e3);
         sv = slot_survives(c32, e0, e1, e2, e3, p, c16, L, R_);
         row[j] = (uint32_t)c16 | (uint32_t)(uint8_t)L << 16 | (uint32_t)(uint8_t)R_ << 24;

@@ -7,7 +7,9 @@ the frame that line calls into. The assembly names every instruction's location 
 so with --at L an instruction counts if some frame of its chain is line L of the source, and it is attributed to the
 line of the frame just inside that one (to L itself when L is the innermost frame): --at the line of k_count's
 `rounds(std::true_type{}, std::true_type{})` call gives the dynamic cold round loop line by line, with everything its
-lines inline (examine, adds, queue) summed into them. Without --at every instruction goes to its innermost line.
+lines inline (examine, adds, queue) summed into them. Without --at every instruction goes to its innermost line, or
+with --outer to the outermost frame of its chain that lies in the source: the kernel body's own lines, each with all
+it inlines (lambdas, helpers) summed into it, which is the account of the per-bucket code around the round loop.
 
 Classes come from the mnemonic's leading prefix alone: v_ (valu), s_ (salu; of these s_cbranch / s_branch, s_nop and
 s_waitcnt are shown apart as branch, nop, wait), ds_ (lds), global_ (vmem), anything else (other). The counts are
@@ -15,6 +17,7 @@ static: a line's instructions once each, whatever path or trip count they have a
 
   python tools/isa_lines.py --kernel k_countILi1ELb1ELb1ELb0E --at 2880 [-DMHMKC_VERDICT=0 ...]
   python tools/isa_lines.py --asm kcount.s --kernel k_countILi1ELb1ELb1ELb0E --at 2880 --lines 2560-2760
+  python tools/isa_lines.py --kernel k_countILi1ELb1ELb1ELb0E --outer      (the kernel body line by line)
   python tools/isa_lines.py --regs k_count      (NumVgprs / ScratchSize / Occupancy of every kernel whose symbol matches)
 """
 from __future__ import annotations
@@ -85,7 +88,7 @@ def chain_of(loc_match, src_name: str):
     return [(f.endswith(src_name), int(l)) for f, l in FRAME.findall(comment)] or [(True, line)]
 
 
-def count(lines, src_name: str, at: int | None):
+def count(lines, src_name: str, at: int | None, outer: bool = False):
     per = defaultdict(lambda: dict.fromkeys(CLASSES, 0))
     chain = []
     for ln in lines:
@@ -98,7 +101,7 @@ def count(lines, src_name: str, at: int | None):
             continue
         if at is None:
             own = [l for s, l in chain if s]
-            key = own[0] if own else 0
+            key = (own[-1] if outer else own[0]) if own else 0
         else:
             idx = [i for i, (s, l) in enumerate(chain) if s and l == at]
             if not idx:
@@ -129,6 +132,7 @@ def main():
     ap.add_argument("--asm", help="an assembly file made with -gline-tables-only -S (default: compile --src)")
     ap.add_argument("--kernel", help="the kernel's symbol, or a part of it that only one function has")
     ap.add_argument("--at", type=int, help="a source line of the kernel's inline chain")
+    ap.add_argument("--outer", action="store_true", help="without --at: attribute to the outermost frame in the source")
     ap.add_argument("--lines", help="LO-HI: print these source lines only (the totals too)")
     ap.add_argument("--per", type=float, default=1.0, help="also print the totals divided by this (records per pass)")
     ap.add_argument("--regs", metavar="PATTERN", help="print NumVgprs / ScratchSize / Occupancy of matching kernels")
@@ -150,7 +154,7 @@ def main():
     if len(hits) != 1:
         raise SystemExit(f"--kernel {args.kernel!r} matches {[h[0] for h in hits]}")
     name, a, b = hits[0]
-    per = count(text[a:b], src.name, args.at)
+    per = count(text[a:b], src.name, args.at, args.outer)
     lo, hi = (int(x) for x in args.lines.split("-")) if args.lines else (0, 1 << 30)
     print(f"# {name}" + (f", frames inside line {args.at}" if args.at else ""))
     print("line   " + " ".join(f"{c:>6}" for c in CLASSES))
