@@ -24,7 +24,8 @@
  *     (replacing the UPC++ supermer store, src/kcount/kmer_dht.cpp:133-149,222-224): RCCL over xGMI
  *     (mhmkc_config.comm_id), or a host-staged transport the caller provides (mhmkc_set_transport: a
  *     UPC++/MPI/gloo host, several nodes, or several ranks sharing one GPU). The traversal of a contigging round
- *     over all ranks' tables is mhmkc_uutigs_ranks, collective over the same transport.
+ *     over all ranks' tables is mhmkc_uutigs_ranks (the replicated build) or mhmkc_uutigs_frags (rank-local
+ *     fragments joined across ranks), collective over the same transport.
  */
 #ifndef MHMKC_H
 #define MHMKC_H
@@ -36,6 +37,7 @@
 extern "C" {
 #endif
 
+/* (14 gained symbols without a new number: mhmkc_uutigs_frags, mhmkc_uutigs_frags_info) */
 #define MHMKC_ABI_VERSION 14
 #define MHMKC_COMM_ID_BYTES 128
 
@@ -502,6 +504,85 @@ typedef struct {
   uint64_t kept_bytes;           /* what stays: this rank's contig arrays and row map */
 } mhmkc_uutig_ranks_info;
 int mhmkc_uutigs_ranks_info(mhmkc_t h, mhmkc_uutig_ranks_info *info);
+
+/* The same uutigs, built from rank-local fragments instead of a replicated union: what
+ * traverse_debruijn_graph does at rank_n() > 1, walking inside a rank and joining the fragments that cross ranks
+ * (connect_frags, src/dbjg_traversal.cpp:291-335,517-567). The contract is mhmkc_uutigs_ranks's, word for word: the
+ * contigs, the owner rule, the order, the global ids and the row map, none of which depend on the number of ranks; after a
+ * successful call mhmkc_uutigs, mhmkc_uutigs_fetch, mhmkc_uutigs_device, mhmkc_uutig_rows[_device], mhmkc_uutigs_info
+ * (n_ctgs, n_bases) and mhmkc_add_ctgs_from(next, h) answer for this rank exactly as after mhmkc_uutigs_ranks. Kept
+ * until the next reset / finish / destroy and counted in mhmkc_stats.device_bytes[_peak].
+ *   One build per finish: whichever of mhmkc_uutigs_ranks and mhmkc_uutigs_frags runs first after a finish builds; a
+ *   later call of either returns the kept values and runs no collective. After a fragment build mhmkc_uutigs_ranks_info
+ *   fills only n_ctgs, n_bases, first_id, n_ctgs_all, n_rows, n_rows_all and kept_bytes (the rest is zero), and after a
+ *   replicated build mhmkc_uutigs_frags_info fills only the same seven.
+ * How: 1. claims: every own port whose routed link (mhmkc_dbjg_links_ranks, built first if the handle has none, which is
+ * itself a collective) is OK and names a row of another rank tells that rank which port it enters; a port is
+ * cross-linked iff its own link is OK, points at another rank and it received the claim of exactly the port it points at,
+ * naming it: the linked-port rule of mhmkc_uutigs with its two halves on two ranks. 2. local ranking: the rank's own
+ * rows under links whose cross-rank neighbours are ends, with mhmkc_uutigs's kernels; what lies between two ends is a
+ * fragment, closed (a contig of the union, cycles on one rank included) when neither end port is cross-linked, else
+ * open. 3. every open fragment's record is gathered on every rank: the only replicated state. 4. every rank ranks the
+ * fragment graph (fragments as rows, cross links as links) by the same pointer jumping with weighted states. 5. a
+ * cross-rank contig belongs to the rank of its start row; every rank sorts its contigs by start key; the ranks gather
+ * their contig counts and the owners the global ids of the cross-rank contigs. 6. every row gets its final place; the
+ * open fragments of contigs another rank owns send that rank their bases, one segment per fragment.
+ * Memory and traffic follow a rank's own rows and the open fragments of all ranks (frags_open_all), not the union's rows;
+ * the fragment graph is replicated, so they shrink to the share of fragments and do not fall as 1 / n_ranks.
+ * Bytes per record moved, per stage: MHMKC_UFRAGS_CLAIMS 12 (claiming row u32, entered row u32, directions u32);
+ * MHMKC_UFRAGS_GATHER 8 NL + 48 (the start key; the sum of the counts; start row and rows; the two end rows; the two
+ * peer rows; start count, ranks and directions; the start's position), sent to every other rank; MHMKC_UFRAGS_IDS 4 (a
+ * cross-rank contig's global id), sent to every other rank; MHMKC_UFRAGS_BASES 1 (a base: a row's, or one of the k - 1
+ * behind a contig's last row). _LOCAL and _RANK move nothing. The fixed-size all-gathers of counts and verdicts between
+ * the stages (a few words per rank) are not counted.
+ * scratch_bytes <= MHMKC_UFRAG_SCRATCH_ROW * n_rows + MHMKC_UFRAG_SCRATCH_FRAG * frags_open_all +
+ *   (k + MHMKC_UFRAG_SCRATCH_CTG) * ctgs_cross_all + n_bases + MHMKC_UFRAG_SCRATCH_FIXED + 16 * n_ranks^2
+ * (n_bases, this rank's kept bases, bounds the bases it receives); nothing is allocated in proportion to the union's
+ * rows. The scratch of a links build inside the call is mhmkc_route_info's.
+ * Collective over the ranks of a finished MHMKC_OWNER_MINIMIZER handle. n_ranks == 1: mhmkc_uutigs with *first_id = 0.
+ * n_ranks > 1 with MHMKC_OWNER_HASH: MHMKC_EUNSUPPORTED; before finish: MHMKC_ESTATE; both before any collective, in that
+ * order. A failure on any rank after the first collective is a failure on every rank: MHMKC_ETRANSPORT on the ranks that
+ * did not fail themselves. Limits: a rank's own rows, the open fragments of all ranks together and the contigs of all
+ * ranks together are each at most 2^32-2 (MHMKC_EUNSUPPORTED beyond, on every rank); the union's rows are not limited,
+ * but one contig's are: n_kmers and the ranking's row counts are 32 bits, as in mhmkc_uutigs, so a contig has at most
+ * 2^32-2 rows. This last limit is not checked.
+ * Any output pointer may be NULL. */
+int mhmkc_uutigs_frags(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases, uint64_t *first_id, uint64_t *n_ctgs_all);
+
+enum { MHMKC_UFRAGS_CLAIMS = 0, MHMKC_UFRAGS_LOCAL = 1, MHMKC_UFRAGS_GATHER = 2, MHMKC_UFRAGS_RANK = 3,
+       MHMKC_UFRAGS_IDS = 4, MHMKC_UFRAGS_BASES = 5, MHMKC_UFRAGS_STAGES = 6 };
+#define MHMKC_UFRAG_CLAIM_BYTES 12
+#define MHMKC_UFRAG_RECORD_BYTES(n_longs) (8 * (n_longs) + 48)
+#define MHMKC_UFRAG_ID_BYTES 4
+#define MHMKC_UFRAG_BASE_BYTES 1
+#define MHMKC_UFRAG_SCRATCH_ROW 320
+#define MHMKC_UFRAG_SCRATCH_FRAG 448
+#define MHMKC_UFRAG_SCRATCH_CTG 8
+#define MHMKC_UFRAG_SCRATCH_FIXED (1 << 20)
+/* How the last mhmkc_uutigs_frags went. Every field is a uint64_t or a double. */
+typedef struct {
+  uint64_t n_ctgs, n_bases;      /* this rank's */
+  uint64_t first_id, n_ctgs_all;
+  uint64_t n_rows, n_rows_all;   /* this rank's rows, the union's */
+  uint64_t frags_open;           /* this rank's fragments with a cross-linked end port */
+  uint64_t frags_open_all;       /* of all ranks: the rows of the replicated fragment graph */
+  uint64_t frags_closed;         /* this rank's fragments that are contigs of the union */
+  uint64_t local_cycles;         /* of them, cycles */
+  uint64_t cross_links;          /* own ports with a mutual link to another rank */
+  uint64_t ctgs_cross_all;       /* contigs made of open fragments, of all ranks */
+  uint64_t ctgs_cross_mine;      /* of them, this rank's */
+  uint64_t cycles_cross_all;     /* of them, cycles */
+  uint64_t rounds_local, cycle_rounds_local; /* pointer-jumping rounds of the local ranking: all ports, cycle ports alone */
+  uint64_t rounds_frags, cycle_rounds_frags; /* the same of the fragment ranking */
+  uint64_t links_built;          /* 1: this call built the routed links first */
+  uint64_t records_sent[MHMKC_UFRAGS_STAGES], records_recv[MHMKC_UFRAGS_STAGES];
+  uint64_t bytes_sent[MHMKC_UFRAGS_STAGES], bytes_recv[MHMKC_UFRAGS_STAGES];
+  double ms_stage[MHMKC_UFRAGS_STAGES]; /* device events on the handle's stream (a stage's move and its host staging included) */
+  double ms_total;
+  uint64_t scratch_bytes;        /* the peak of the build's device memory above what stays */
+  uint64_t kept_bytes;           /* what stays: this rank's contig arrays and row map */
+} mhmkc_uutig_frags_info;
+int mhmkc_uutigs_frags_info(mhmkc_t h, mhmkc_uutig_frags_info *info);
 
 /* Queries answered by the rank that owns the key, and every row's de Bruijn links with neighbours on any rank
  * (DESIGN.md §3.11b). The reference's traversal computes get_kmer_target_rank of a neighbour and asks that rank by rpc

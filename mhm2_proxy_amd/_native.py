@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "mhmkc_wait_stream", "mhmkc_set_dmin_thres", "mhmkc_set_transport", "mhmkc_minimizer_hashes",
     "mhmkc_lookup", "mhmkc_lookup_device", "mhmkc_dbjg_links", "mhmkc_dbjg_links_device",
     "mhmkc_uutigs", "mhmkc_uutigs_fetch", "mhmkc_uutigs_device", "mhmkc_uutig_rows", "mhmkc_uutig_rows_device",
-    "mhmkc_uutigs_info", "mhmkc_uutigs_ranks", "mhmkc_uutigs_ranks_info",
+    "mhmkc_uutigs_info", "mhmkc_uutigs_ranks", "mhmkc_uutigs_ranks_info", "mhmkc_uutigs_frags", "mhmkc_uutigs_frags_info",
     "mhmkc_add_ctgs_device", "mhmkc_add_ctgs_from", "mhmkc_ctgs_ranks_info",
     "mhmkc_lookup_ranks", "mhmkc_lookup_ranks_device", "mhmkc_dbjg_links_ranks", "mhmkc_dbjg_links_ranks_fetch",
     "mhmkc_dbjg_links_ranks_device", "mhmkc_route_info",
@@ -60,6 +60,10 @@ ABI_SYMBOLS = [
 MHMKC_DEPTH_U16, MHMKC_DEPTH_F64 = 0, 1
 UUTIG_MAX_ROUNDS = 48
 URANKS_STAGES = ("gather", "build", "select")  # MHMKC_URANKS_*
+UFRAGS_STAGES = ("claims", "local", "gather", "rank", "ids", "bases")  # MHMKC_UFRAGS_*
+# bytes per record moved (MHMKC_UFRAG_*_BYTES; "gather": plus 8 per key word) and the scratch bound's constants
+UFRAG_RECORD_BYTES = {"claims": 12, "gather": 48, "ids": 4, "bases": 1}
+UFRAG_SCRATCH_ROW, UFRAG_SCRATCH_FRAG, UFRAG_SCRATCH_CTG, UFRAG_SCRATCH_FIXED = 320, 448, 8, 1 << 20
 ROUTE_STAGES = ("route", "exchange", "answer", "return", "unpack")  # MHMKC_ROUTE_*
 SYNTH_SYMBOLS = ["mhmkc_synth_config_init", "mhmkc_synth_genome", "mhmkc_synth_reads"]
 # the test-only entry point (include/mhmkc_debug.h)
@@ -92,6 +96,24 @@ class MhmkcUutigRanksInfo(C.Structure):
         d = {f: getattr(self, f) for f, t in self._fields_ if t in (C.c_uint64, C.c_double)}
         for f in self._PER_STAGE + ("ms_stage",):
             d[f] = dict(zip(URANKS_STAGES, list(getattr(self, f))))
+        return d
+
+
+class MhmkcUutigFragsInfo(C.Structure):
+    """mhmkc_uutig_frags_info (include/mhmkc.h)."""
+    _PER_STAGE = ("records_sent", "records_recv", "bytes_sent", "bytes_recv")
+    _fields_ = [(f, C.c_uint64) for f in ("n_ctgs", "n_bases", "first_id", "n_ctgs_all", "n_rows", "n_rows_all",
+                                          "frags_open", "frags_open_all", "frags_closed", "local_cycles", "cross_links",
+                                          "ctgs_cross_all", "ctgs_cross_mine", "cycles_cross_all", "rounds_local",
+                                          "cycle_rounds_local", "rounds_frags", "cycle_rounds_frags", "links_built")] + \
+               [(f, C.c_uint64 * len(UFRAGS_STAGES)) for f in _PER_STAGE] + \
+               [("ms_stage", C.c_double * len(UFRAGS_STAGES)), ("ms_total", C.c_double),
+                ("scratch_bytes", C.c_uint64), ("kept_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, t in self._fields_ if t in (C.c_uint64, C.c_double)}
+        for f in self._PER_STAGE + ("ms_stage",):
+            d[f] = dict(zip(UFRAGS_STAGES, list(getattr(self, f))))
         return d
 
 
@@ -324,6 +346,8 @@ def lib() -> C.CDLL:
     L.mhmkc_uutigs_info.argtypes = [VP, P(MhmkcUutigInfo)]
     L.mhmkc_uutigs_ranks.argtypes = [VP, P(U64), P(U64), P(U64), P(U64)]
     L.mhmkc_uutigs_ranks_info.argtypes = [VP, P(MhmkcUutigRanksInfo)]
+    L.mhmkc_uutigs_frags.argtypes = [VP, P(U64), P(U64), P(U64), P(U64)]
+    L.mhmkc_uutigs_frags_info.argtypes = [VP, P(MhmkcUutigFragsInfo)]
     L.mhmkc_ctgs_ranks_info.argtypes = [VP, P(MhmkcCtgRanksInfo)]
     L.mhmkc_lookup_ranks.argtypes = [VP, VP, U64, I32, VP, VP, VP, VP, VP]
     L.mhmkc_lookup_ranks_device.argtypes = [VP, VP, U64, I32, VP, VP, VP, VP, VP]

@@ -32,7 +32,7 @@ ORACLE = ROOT / "oracle" / "liboracle.so"
 LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kcount_ctgin.hip", CSRC / "kcount_ctgx.hip",
                CSRC / "kcount_owner.hip",
                CSRC / "kcount_query.hip", CSRC / "kcount_route.hip",
-               CSRC / "kcount_uutig.hip", CSRC / "kcount_uutig_ranks.hip",
+               CSRC / "kcount_uutig.hip", CSRC / "kcount_uutig_ranks.hip", CSRC / "kcount_uutig_frags.hip",
                CSRC / "fastq.hip",
                CSRC / "mhmkc_host.cpp"]
 LIB_DEPS = LIB_SOURCES + [CSRC / "kcount_launch.hpp", CSRC / "kcount_query_dev.hpp", CSRC / "kmer_ops.hpp", ROOT / "include" / "mhmkc.h"]

@@ -591,4 +591,93 @@ hipError_t launch_uutig_ranks_rows(const uint32_t *urow_ctg, const uint32_t *uro
                                    uint64_t n_rows, uint64_t base_me, uint64_t n_me, const uint32_t *gid, uint64_t n_ctgs,
                                    uint32_t *row_ctg, uint32_t *row_pos, uint8_t *row_rc, hipStream_t s);
 
+// The uutigs of the union from rank-local fragments (kcount_uutig_frags.hip). Routed links: entry
+// d * n + i of rl_row / rl_rank / rl_status (mhmkc_dbjg_links_ranks). A claim is three u32 (MHMKC_UFRAG_CLAIM_BYTES). An
+// open fragment's record is its start key (nl words, in keys) and UFRAG_REST_WORDS words (in rest):
+//   0 the sum of its rows' counts; 1 start row | rows << 32; 2 the rows of its end ports 0 | 1 << 32; 3 the rows of their
+//   peer ports; 4 start count | rank << 16 | peer ranks << 24, << 32 | end directions << 40, 41 | peer directions << 42, 43 |
+//   has a peer << 44, 45; 5 the start row's position in the fragment.
+// Fragment f has the ports 2 f + y, y the end; fragments of rank r lie at [base[r], base[r + 1]) of the gathered records.
+constexpr int UFRAG_REST_WORDS = 6;
+enum { UFRAG_C_OPEN = 0, UFRAG_C_CLOSED, UFRAG_C_CYCLES, UFRAG_C_LINKS, UFRAG_C_STARTS, UFRAG_C_MINE, UFRAG_C_XCYCLES,
+       UFRAG_C_BAD, UFRAG_C_ACTIVE, UFRAG_COUNTERS };
+// the replicated fragment graph after its ranking: entry [2 nf] the port a port enters (all ones: an end), st [2 nf] the
+// ranking states, comp [nf] the contig's start fragment, off [nf] the contig's rows before the fragment, flag [nf] (1
+// reversed against the start fragment, 2 a start fragment, 4 of a cycle), cidx [nf + 1] a start fragment's place among
+// the xc cross-rank contigs, gid [xc] their global ids
+struct UfragGraph {
+  const uint64_t *keys, *rest;
+  uint64_t nf;
+  int nl;
+  const uint64_t *entry;
+  const UutigPort *st;
+  const uint32_t *comp, *off;
+  const uint8_t *flag;
+  const uint32_t *cidx, *gid;
+  uint64_t xc;
+};
+// hist[r] += the claims this rank sends rank r (zero first)
+hipError_t launch_ufrag_claim_count(uint64_t n, int me, int g, const uint8_t *rl_rank, const uint8_t *rl_status,
+                                    unsigned long long *hist, hipStream_t s);
+// the claims grouped by receiver from cursor[r] on (the receivers' first places, advanced by the kernel); send holds cap
+hipError_t launch_ufrag_claim_pack(uint64_t n, int me, int g, const uint32_t *rl_row, const uint8_t *rl_rank,
+                                   const uint8_t *rl_status, unsigned long long *cursor, uint64_t cap, uint32_t *send,
+                                   hipStream_t s);
+// xlink[2 * row + d] = 1 for every own port a received claim of rank `from` cross-links (zero first); *n_links += them
+hipError_t launch_ufrag_claim_match(const uint32_t *recv, uint64_t n_recv, int from, uint64_t n, const uint32_t *rl_row,
+                                    const uint8_t *rl_rank, const uint8_t *rl_status, uint8_t *xlink,
+                                    unsigned long long *n_links, hipStream_t s);
+// next / status [2 n] in mhmkc_dbjg_links's layout for the rank's own table: a link to another rank is an end
+hipError_t launch_ufrag_local_links(uint64_t n, int me, const uint32_t *rl_row, const uint8_t *rl_rank,
+                                    const uint8_t *rl_status, uint32_t *next, uint8_t *status, hipStream_t s);
+// row_ctg[start] = the fragment's index in starts; lf_open [n_frag]: its place among the rank's records or 0xFFFFFFFF;
+// closed fragments' starts appended to cstarts [n]; ctr: UFRAG_C_OPEN, _CLOSED, _CYCLES, _STARTS, _BAD
+hipError_t launch_ufrag_classify(const uint32_t *starts, uint64_t n_frag, uint64_t n, const UutigPort *st,
+                                 const uint8_t *xlink, const uint32_t *next, const uint8_t *status, uint32_t *row_ctg,
+                                 uint32_t *lf_open, uint32_t *cstarts, unsigned long long *ctr, hipStream_t s);
+hipError_t launch_ufrag_emit(const OutRows &t, uint64_t n, int nl, int nlo, const uint32_t *starts, uint64_t n_frag,
+                             const UutigPort *st, const uint8_t *xlink, const uint32_t *rl_row, const uint8_t *rl_rank,
+                             const uint8_t *rl_status, const uint32_t *lf_open, int me, uint64_t n_open, uint64_t *keys,
+                             uint64_t *rest, hipStream_t s);
+// rocprim's scratch for the sorts and scans of these launches over at most n_items items
+size_t ufrag_tmp_bytes(uint64_t n_items);
+size_t ufrag_resolve_scratch_bytes(uint64_t nf);
+hipError_t launch_ufrag_resolve(const uint64_t *rest, uint64_t nf, void *scratch, size_t scratch_bytes, void *tmp,
+                                size_t tmp_bytes, uint64_t *entry, hipStream_t s);
+// launch_uutig_init for the fragment graph: weighted states (dist: the rows of the fragment entered, sum: the fragment's)
+hipError_t launch_ufrag_init(const uint64_t *keys, const uint64_t *rest, uint64_t nf, int nl, const uint64_t *entry,
+                             const uint64_t *list, uint64_t n_items, const UutigPort *cut, uint32_t round, UutigPort *st,
+                             hipStream_t s);
+// comp / off / flag, isstart [nf + 1] and its exclusive scan cidx [nf + 1]; ctr: UFRAG_C_XCYCLES, _BAD
+hipError_t launch_ufrag_place(const uint64_t *keys, uint64_t nf, int nl, const UutigPort *st, const uint64_t *entry,
+                              uint32_t *comp, uint32_t *off, uint8_t *flag, uint32_t *isstart, uint32_t *cidx, void *tmp,
+                              size_t tmp_bytes, unsigned long long *ctr, hipStream_t s);
+// the start rows of the start fragments in [f0, f1) appended to cstarts; ctr: UFRAG_C_STARTS, _MINE
+hipError_t launch_ufrag_owned(const uint64_t *rest, uint64_t f0, uint64_t f1, uint64_t nf, const uint8_t *flag, uint64_t n,
+                              uint32_t *cstarts, unsigned long long *ctr, hipStream_t s);
+size_t ufrag_table_scratch_bytes(uint64_t n_ctgs);
+// cstarts sorted by key; n_kmers / depths [n_ctgs], offsets [n_ctgs + 1]; lf_ctg[fragment] = its contig here; gid of the
+// cross-rank contigs this rank owns (rst: the states of the local ranking; f0, n_open: the rank's records)
+hipError_t launch_ufrag_table(const OutRows &t, uint64_t n, int k, int nl, int nlo, uint32_t *cstarts, uint64_t n_ctgs,
+                              const UutigPort *rst, const uint32_t *row_ctg, const uint32_t *lf_open, uint32_t *lf_ctg,
+                              uint64_t n_frag, uint64_t f0, uint64_t n_open, const UfragGraph &g, uint64_t first_id,
+                              uint32_t *gid, void *scratch, size_t scratch_bytes, void *tmp, size_t tmp_bytes,
+                              uint32_t *n_kmers, double *depths, uint64_t *offsets, hipStream_t s);
+size_t ufrag_segs_scratch_bytes(uint64_t nf);
+// seg_pos [nf]: the place of every fragment's segment in the layout grouped by (sender, owner), in fragment order inside
+// a group; glen [g * g] += the groups' bytes (zero first)
+hipError_t launch_ufrag_segs(const UfragGraph &g, int k, int n_ranks, void *scratch, size_t scratch_bytes, void *tmp,
+                             size_t tmp_bytes, uint64_t *seg_pos, unsigned long long *glen, hipStream_t s);
+// the final row map (global ids) from the fragment-local one, and every own row's bases: into seqs, or into send at
+// seg_pos[fragment] - seg_base
+hipError_t launch_ufrag_rows(const OutRows &t, uint64_t n, int k, int nl, int nlo, uint32_t *row_ctg, uint32_t *row_pos,
+                             uint8_t *row_rc, const uint32_t *lf_open, const uint32_t *lf_ctg, uint64_t n_frag, uint64_t f0,
+                             uint64_t n_open, const UfragGraph &g, int me, uint64_t first_id, uint64_t n_ctgs,
+                             const uint64_t *offsets, const uint32_t *n_kmers, uint64_t n_bases, char *seqs,
+                             const uint64_t *seg_pos, uint64_t seg_base, uint64_t send_bytes, char *send, hipStream_t s);
+// the received segments (of rank r at seg_pos + recv_base[r] of recv) into the contigs this rank owns
+hipError_t launch_ufrag_scatter(const UfragGraph &g, int k, int me, int n_ranks, uint64_t first_id, uint64_t n_ctgs,
+                                const uint64_t *offsets, uint64_t n_bases, char *seqs, const uint64_t *seg_pos,
+                                const uint64_t *recv_base, const char *recv, uint64_t recv_bytes, hipStream_t s);
+
 }  // namespace mhm

@@ -523,6 +523,28 @@ struct mhmkc {
     d_ursel.release();
     d_urk.release();
   }
+  // the same state built from rank-local fragments (mhmkc_uutigs_frags, kcount_uutig_frags.hip). All of
+  // d_uf is one build's scratch, released before uutigs_frags() returns: the local links and cross-link marks, the two
+  // state buffers of the local ranking, the per-fragment lists, the counters and rank tables, the cycle ports, the claims
+  // sent and received; the gathered records (keys, rest), the fragment ports' entries, the fragment ranking's two state
+  // buffers, its per-fragment results, the sort / segment work area, its cycle ports; rocprim's scratch, the cross-rank
+  // contigs' ids, the contig table's sort scratch, the bases sent and received.
+  enum { UF_LOC, UF_A, UF_B, UF_AUX, UF_CTR, UF_LIST, UF_CSEND, UF_CRECV, UF_KEYS, UF_REST, UF_ENT, UF_FA, UF_FB, UF_META,
+         UF_WORK, UF_FLIST, UF_TMP, UF_GID, UF_TBL, UF_BSEND, UF_BRECV, UF_BUFS };
+  DevBuf d_uf[UF_BUFS];
+  mhmkc_uutig_frags_info finfo{};
+  bool ufrags_built = false;  // the kept state is a fragment build's (cleared with uranks_ready)
+  int uutigs_frags();
+  int uutigs_frags_build(std::vector<hipEvent_t> &evs);
+  // list ranking of n rows' 2 n ports by pointer jumping, cycles opened at their start and ranked again (the loop of
+  // uutigs_build over any port graph): init writes the first states of all ports (list null) or of the listed ones
+  typedef std::function<hipError_t(const uint64_t *list, uint64_t n_items, const mhm::UutigPort *cut, uint32_t round,
+                                   mhm::UutigPort *st)> PortInit;
+  int rank_ports(uint64_t n, const uint64_t *keys, int key_nl, int key_nlo, const PortInit &init, mhm::UutigPort *&F,
+                 mhm::UutigPort *&G, unsigned long long *cnt, DevBuf &list_buf, uint64_t &rounds, uint64_t &cycle_rounds);
+  void drop_ufrags_scratch() {
+    for (DevBuf &b : d_uf) b.release();
+  }
   // queries routed to the owner rank (kcount_route.hip). d_rt_ask (a round's send layout, replies,
   // places, owners, the per-rank tables) and d_rt_recv (the received queries and their replies) are one call's scratch;
   // d_rlinks keeps mhmkc_dbjg_links_ranks's arrays (next_row u32, next_rank u8, status u8, 2 n_out entries each) until
@@ -547,7 +569,7 @@ struct mhmkc {
   }
   void drop_query() {
     drop_uranks_scratch();
-    uranks_ready = false;
+    uranks_ready = ufrags_built = false;
     ur_first = ur_all = 0;
     d_qidx.release();
     d_links.release();
@@ -4601,6 +4623,7 @@ int mhmkc::uutigs_build(std::vector<hipEvent_t> &evs) {
     return hip_fail(e, "uutig ports");
   const int t1 = mark();
 
+  // (stages 1 to 3 have a twin for any port graph, rank_ports below, used by uutigs_frags_build: keep the two alike)
   // stage 2: pointer jumping. After round r a port is done iff its end is at most 2^r - 1 ports away, so as long as a
   // path is unfinished the count of ports under way falls; once it stands still, what is left lies on cycles
   int max_rounds = 1;
@@ -4971,6 +4994,550 @@ int mhmkc::uutigs_ranks() {
   return rc;
 }
 
+// NOTE: this is a second copy of the loop in uutigs_build (stages 1 to 3 there), kept apart so that uutigs_build and with
+// it mhmkc_uutigs / mhmkc_uutigs_ranks stay exactly as their tests pin them. A fix to the rounds, the stand-still test or
+// the cycle phase belongs in BOTH places; uutigs_build can call this function once that is wanted.
+// The ranking of uutigs_build (its stages 1 to 3) over any graph of n rows with two ports each: the first states from
+// init, pointer jumping until the count of ports under way stands still, then the cycles: more rounds over their ports
+// alone until each knows its start, opened there (init with cut) and ranked as paths. The last states are in F.
+int mhmkc::rank_ports(uint64_t n, const uint64_t *keys, int key_nl, int key_nlo, const PortInit &init, mhm::UutigPort *&F,
+                      mhm::UutigPort *&G, unsigned long long *cnt, DevBuf &list_buf, uint64_t &rounds,
+                      uint64_t &cycle_rounds) {
+  hipError_t e;
+  auto count_back = [&](uint64_t &v) -> hipError_t {
+    unsigned long long x = 0;
+    hipError_t r = hipMemcpyAsync(&x, cnt, 8, hipMemcpyDeviceToHost, stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(stream);
+    v = x;
+    return r;
+  };
+  rounds = cycle_rounds = 0;
+  uint32_t round = 0;
+  if ((e = init(nullptr, 2 * n, nullptr, round, F)) != hipSuccess) return hip_fail(e, "uutig ports");
+  int max_rounds = 1;
+  while ((1ull << max_rounds) < 2 * n) max_rounds++;
+  max_rounds++;
+  uint64_t active = 0, prev = ~0ull;
+  int done = 0;
+  while (done < max_rounds) {
+    round++;
+    if ((e = hipMemsetAsync(cnt, 0, 8, stream)) != hipSuccess ||
+        (e = mhm::launch_uutig_jump(F, G, n, nullptr, 2 * n, keys, key_nl, key_nlo, round, cnt, stream)) != hipSuccess ||
+        (e = count_back(active)) != hipSuccess)
+      return hip_fail(e, "uutig ranking");
+    done++;
+    std::swap(F, G);
+    if (!active || active == prev) break;
+    prev = active;
+  }
+  rounds = (uint64_t)done;
+  if (!active) return MHMKC_OK;
+  const uint64_t n_list = active;
+  if (n_list > 2 * n) return fail(MHMKC_EHIP, "uutigs: %llu of %llu ports under way", (unsigned long long)n_list,
+                                  (unsigned long long)(2 * n));
+  if ((e = grow(list_buf, n_list * 8)) != hipSuccess) return hip_fail(e, "uutig cycles");
+  uint64_t *list = list_buf.as<uint64_t>();
+  if ((e = hipMemsetAsync(cnt, 0, 8, stream)) != hipSuccess ||
+      (e = mhm::launch_uutig_active(F, n, list, n_list, cnt, stream)) != hipSuccess)
+    return hip_fail(e, "uutig cycles");
+  int extra = std::max(0, max_rounds - done);
+  extra += extra & 1;  // an even number: the last states are in F again, where the paths' are
+  for (int x = 0; x < extra; x++) {
+    round++;
+    if ((e = mhm::launch_uutig_jump(F, G, n, list, n_list, keys, key_nl, key_nlo, round, cnt, stream)) != hipSuccess)
+      return hip_fail(e, "uutig cycles");
+    std::swap(F, G);
+    cycle_rounds++;
+  }
+  round++;
+  if ((e = init(list, n_list, F, round, F)) != hipSuccess) return hip_fail(e, "uutig cycles");
+  mhm::UutigPort *const F0 = F;
+  uint64_t left = n_list;
+  for (int x = 0; left && x <= max_rounds; x++) {
+    round++;
+    if ((e = hipMemsetAsync(cnt, 0, 8, stream)) != hipSuccess ||
+        (e = mhm::launch_uutig_jump(F, G, n, list, n_list, keys, key_nl, key_nlo, round, cnt, stream)) != hipSuccess ||
+        (e = count_back(left)) != hipSuccess)
+      return hip_fail(e, "uutig cycles");
+    std::swap(F, G);
+    cycle_rounds++;
+  }
+  if (left) return fail(MHMKC_EHIP, "uutigs: %llu ports of opened cycles never reached an end", (unsigned long long)left);
+  if (F != F0) {  // one more round copies the ports that were done last into the paths' buffer
+    round++;
+    if ((e = mhm::launch_uutig_jump(F, G, n, list, n_list, keys, key_nl, key_nlo, round, cnt, stream)) != hipSuccess)
+      return hip_fail(e, "uutig cycles");
+    std::swap(F, G);
+    cycle_rounds++;
+  }
+  return MHMKC_OK;
+}
+
+// The uutigs of the union of all ranks' tables from rank-local fragments. Collectives, in this order on
+// every rank: the claim counts and row counts; a verdict; the claims; the open fragments' counts; a verdict; the records;
+// the contig counts; a verdict; the cross-rank contigs' ids; a verdict; the bases; the status. Every all-gather carries
+// the rank's failed flag, and every decision that leads into a move or past one is taken from gathered values: a rank
+// that fails alone (lrc) reports at the next all-gather, where every rank returns.
+int mhmkc::uutigs_frags_build(std::vector<hipEvent_t> &evs) {
+  const int g = G(), me = cfg.rank;
+  const uint64_t n = n_out;
+  hipError_t e = hipSuccess;
+  int rc, lrc = MHMKC_OK;
+  std::string lerr;
+  auto lfail = [&](int r) {
+    if (r && !lrc) {
+      lrc = r;
+      lerr = err;
+    }
+  };
+  auto hfail = [&](hipError_t x, const char *what) {
+    if (x != hipSuccess) lfail(x == hipErrorOutOfMemory ? fail(MHMKC_ENOMEM, "uutigs_frags: %s", what) : hip_fail(x, what));
+  };
+  auto mark = [&]() -> int {
+    hipEvent_t ev;
+    if (hipEventCreate(&ev) != hipSuccess) return -1;
+    (void)hipEventRecord(ev, stream);
+    evs.push_back(ev);
+    return (int)evs.size() - 1;
+  };
+  auto ms = [&](int a, int b) -> double {
+    float f = 0;
+    if (a < 0 || b < 0 || hipEventElapsedTime(&f, evs[(size_t)a], evs[(size_t)b]) != hipSuccess) return 0;
+    return (double)f;
+  };
+  // nv words of every rank, with its failed flag behind them: all[r * (nv + 1) + i]
+  std::vector<uint64_t> all;
+  auto gather = [&](const uint64_t *vals, size_t nv) -> int {
+    std::vector<uint64_t> mine(nv + 1, 0);
+    for (size_t i = 0; i < nv; i++) mine[i] = vals[i];
+    mine[nv] = lrc ? 1 : 0;
+    all.assign((nv + 1) * (size_t)g, 0);
+    if ((rc = allgather_host(mine.data(), all.data(), 8 * (nv + 1)))) return rc;
+    if (lrc) {
+      err = lerr;
+      return lrc;
+    }
+    for (int r = 0; r < g; r++)
+      if (all[(size_t)r * (nv + 1) + nv])
+        return fail(MHMKC_ETRANSPORT, "uutigs_frags: rank %d failed (its mhmkc_last_error says why)", r);
+    return MHMKC_OK;
+  };
+  auto moved = [&](int stage, uint64_t rs, uint64_t rr, uint64_t bs, uint64_t br) {
+    finfo.records_sent[stage] += rs;
+    finfo.records_recv[stage] += rr;
+    finfo.bytes_sent[stage] += bs;
+    finfo.bytes_recv[stage] += br;
+  };
+  auto quiet_move = [&](const std::vector<Xfer> &snd, const std::vector<Xfer> &rcv) -> int {
+    const uint64_t sent0 = st.bytes_sent, recv0 = st.bytes_recv;  // (bytes_* count the record exchange only)
+    const int r = move(snd, rcv);
+    st.bytes_sent = sent0;
+    st.bytes_recv = recv0;
+    return r;
+  };
+  const uint32_t *rrow = n ? rl_row() : nullptr;
+  const uint8_t *rrank = n ? rl_rank() : nullptr, *rstat = n ? rl_status() : nullptr;
+  finfo.n_rows = n;
+  const int t0 = mark();
+
+  // 1. the claims. The counters and rank tables: ctr, hist [g], cursor [g], recv_base [g], glen [g * g]
+  const size_t ctr_b = 8 * ((size_t)mhm::UFRAG_COUNTERS + 3 * (size_t)g + (size_t)g * g);
+  const size_t l4 = align_up(2 * n * 4, 256), l1 = align_up(2 * n, 256);
+  hfail(grow(d_uf[UF_CTR], ctr_b + 64), "counters");
+  if (!lrc && n) hfail(grow(d_uf[UF_LOC], l4 + 2 * l1 + 64), "local links");
+  unsigned long long *ctr = d_uf[UF_CTR].as<unsigned long long>(), *d_hist = ctr + mhm::UFRAG_COUNTERS, *d_cursor = d_hist + g,
+                     *d_rbase = d_cursor + g, *d_glen = d_rbase + g;
+  uint32_t *lnext = d_uf[UF_LOC].as<uint32_t>();
+  uint8_t *lstat = (uint8_t *)(d_uf[UF_LOC].as<char>() + l4), *xlink = lstat + l1;
+  std::vector<uint64_t> hist((size_t)g + 1, 0);
+  if (!lrc) {
+    if ((e = hipMemsetAsync(ctr, 0, ctr_b, stream)) != hipSuccess ||
+        (n && (e = hipMemsetAsync(xlink, 0, 2 * n, stream)) != hipSuccess) ||
+        (n < 0xffffffffull && (e = mhm::launch_ufrag_claim_count(n, me, g, rrank, rstat, d_hist, stream)) != hipSuccess) ||
+        (e = hipMemcpyAsync(hist.data(), d_hist, 8 * (size_t)g, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream)) != hipSuccess) {
+      hfail(e, "claim counts");
+      std::fill(hist.begin(), hist.end(), 0);
+    }
+  }
+  hist[(size_t)me] = 0;
+  hist[(size_t)g] = n;
+  if ((rc = gather(hist.data(), (size_t)g + 1))) return rc;
+  const size_t gw = (size_t)g + 2;
+  std::vector<uint64_t> cm((size_t)g * g, 0);  // cm[from * g + to]: the claims
+  uint64_t N = 0, claims_all = 0;
+  for (int r = 0; r < g; r++) {
+    const uint64_t nr = all[(size_t)r * gw + g];
+    if (nr >= 0xffffffffull)  // (every rank sees the same counts)
+      return fail(MHMKC_EUNSUPPORTED, "uutigs_frags: rank %d has %llu rows, at most 2^32-2", r, (unsigned long long)nr);
+    N += nr;
+    for (int q = 0; q < g; q++) claims_all += (cm[(size_t)r * g + q] = q == r ? 0 : all[(size_t)r * gw + q]);
+  }
+  finfo.n_rows_all = N;
+  std::vector<uint64_t> cstart((size_t)g, 0), croff((size_t)g, 0);
+  uint64_t c_send = 0, c_recv = 0;
+  for (int p = 0; p < g; p++) {
+    cstart[(size_t)p] = c_send;
+    c_send += cm[(size_t)me * g + p];
+    croff[(size_t)p] = c_recv;
+    c_recv += cm[(size_t)p * g + me];
+  }
+  if (c_send > 2 * n) lfail(fail(MHMKC_EHIP, "uutigs_frags: %llu claims of %llu ports", (unsigned long long)c_send,
+                                 (unsigned long long)(2 * n)));
+  if (!lrc && c_send) hfail(grow(d_uf[UF_CSEND], c_send * 12 + 64), "claims");
+  if (!lrc && c_recv) hfail(grow(d_uf[UF_CRECV], c_recv * 12 + 64), "received claims");
+  if (!lrc && c_send &&
+      ((e = hipMemcpyAsync(d_cursor, cstart.data(), 8 * (size_t)g, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+       (e = mhm::launch_ufrag_claim_pack(n, me, g, rrow, rrank, rstat, d_cursor, c_send, d_uf[UF_CSEND].as<uint32_t>(),
+                                         stream)) != hipSuccess ||
+       (e = hipStreamSynchronize(stream)) != hipSuccess))
+    hfail(e, "claims");
+  if ((rc = gather(nullptr, 0))) return rc;
+  std::vector<Xfer> snd, rcv;
+  if (claims_all) {
+    for (int p = 0; p < g; p++) {
+      if (p == me) continue;
+      if (cm[(size_t)me * g + p])
+        snd.push_back({p, d_uf[UF_CSEND].as<char>() + cstart[(size_t)p] * 12, cm[(size_t)me * g + p] * 12});
+      if (cm[(size_t)p * g + me])
+        rcv.push_back({p, d_uf[UF_CRECV].as<char>() + croff[(size_t)p] * 12, cm[(size_t)p * g + me] * 12});
+    }
+    if ((rc = quiet_move(snd, rcv))) return rc;
+    moved(MHMKC_UFRAGS_CLAIMS, c_send, c_recv, c_send * 12, c_recv * 12);
+  }
+  const int t1 = mark();
+
+  // 2. the local ranking: cross-linked ports, the rank's own links, its fragments
+  const size_t rows_b = align_up(n * 4, 256), a4 = align_up(n * 4 + 4, 256);
+  uint32_t *row_ctg = nullptr, *row_pos = nullptr, *starts = nullptr, *cstarts = nullptr, *lf_open = nullptr, *lf_ctg = nullptr;
+  uint8_t *row_rc = nullptr;
+  mhm::UutigPort *RF = nullptr, *RG = nullptr;
+  uint64_t n_frag = 0, n_open = 0;
+  std::vector<unsigned long long> hc((size_t)mhm::UFRAG_COUNTERS, 0);
+  auto counters = [&]() -> hipError_t {
+    hipError_t r = hipMemcpyAsync(hc.data(), ctr, 8 * (size_t)mhm::UFRAG_COUNTERS, hipMemcpyDeviceToHost, stream);
+    return r == hipSuccess ? hipStreamSynchronize(stream) : r;
+  };
+  if (!lrc && n) {
+    for (int p = 0; p < g && e == hipSuccess; p++)
+      if (p != me && cm[(size_t)p * g + me])
+        e = mhm::launch_ufrag_claim_match(d_uf[UF_CRECV].as<uint32_t>() + croff[(size_t)p] * 3, cm[(size_t)p * g + me], p, n,
+                                          rrow, rrank, rstat, xlink, ctr + mhm::UFRAG_C_LINKS, stream);
+    if (e == hipSuccess) e = mhm::launch_ufrag_local_links(n, me, rrow, rrank, rstat, lnext, lstat, stream);
+    if (e == hipSuccess) e = grow(d_urows, 2 * rows_b + n + 64);
+    if (e == hipSuccess) e = grow(d_uf[UF_A], 2 * n * sizeof(mhm::UutigPort));
+    if (e == hipSuccess) e = grow(d_uf[UF_B], 2 * n * sizeof(mhm::UutigPort));
+    if (e == hipSuccess) e = grow(d_uf[UF_AUX], 4 * a4 + 64);
+    hfail(e, "ranking scratch");
+  }
+  if (!lrc && n) {
+    row_ctg = d_urows.as<uint32_t>();
+    row_pos = (uint32_t *)(d_urows.as<char>() + rows_b);
+    row_rc = (uint8_t *)(d_urows.as<char>() + 2 * rows_b);
+    starts = d_uf[UF_AUX].as<uint32_t>();
+    cstarts = (uint32_t *)(d_uf[UF_AUX].as<char>() + a4);
+    lf_open = (uint32_t *)(d_uf[UF_AUX].as<char>() + 2 * a4);
+    lf_ctg = (uint32_t *)(d_uf[UF_AUX].as<char>() + 3 * a4);
+    RF = d_uf[UF_A].as<mhm::UutigPort>();
+    RG = d_uf[UF_B].as<mhm::UutigPort>();
+    const mhm::OutRows t = out_rows();
+    const int rnlo = nlo;
+    lfail(rank_ports(n, d_out_keys.as<uint64_t>(), nl, nlo,
+                     [&, t, rnlo](const uint64_t *list, uint64_t n_items, const mhm::UutigPort *cut, uint32_t round,
+                                  mhm::UutigPort *s) {
+                       return mhm::launch_uutig_init(t, n, rnlo, lnext, lstat, list, n_items, cut, round, s, stream);
+                     },
+                     RF, RG, ctr + mhm::UFRAG_C_ACTIVE, d_uf[UF_LIST], finfo.rounds_local, finfo.cycle_rounds_local));
+    if (!lrc) {
+      uint64_t nf0 = 0;
+      if ((e = hipMemsetAsync(ctr + mhm::UFRAG_C_ACTIVE, 0, 8, stream)) != hipSuccess ||
+          (e = mhm::launch_uutig_starts(t, n, nl, nlo, RF, row_ctg, row_pos, row_rc, starts, ctr + mhm::UFRAG_C_ACTIVE,
+                                        stream)) != hipSuccess ||
+          (e = counters()) != hipSuccess)
+        hfail(e, "fragment starts");
+      nf0 = hc[mhm::UFRAG_C_ACTIVE];
+      if (!lrc && nf0 > n) lfail(fail(MHMKC_EHIP, "uutigs_frags: %llu starts in %llu rows", (unsigned long long)nf0,
+                                      (unsigned long long)n));
+      if (!lrc) {
+        n_frag = nf0;
+        if ((e = mhm::launch_ufrag_classify(starts, n_frag, n, RF, xlink, lnext, lstat, row_ctg, lf_open, cstarts, ctr,
+                                            stream)) != hipSuccess ||
+            (e = mhm::launch_uutig_place(t, n, RF, row_ctg, row_pos, row_rc, stream)) != hipSuccess ||
+            (e = counters()) != hipSuccess)
+          hfail(e, "fragments");
+        if (!lrc && hc[mhm::UFRAG_C_BAD]) lfail(fail(MHMKC_EHIP, "uutigs_frags: a fragment's start or end lies outside the table"));
+        if (!lrc && hc[mhm::UFRAG_C_OPEN] + hc[mhm::UFRAG_C_CLOSED] != n_frag)
+          lfail(fail(MHMKC_EHIP, "uutigs_frags: the fragments do not add up"));
+        if (!lrc) n_open = hc[mhm::UFRAG_C_OPEN];
+      }
+    }
+  }
+  finfo.frags_open = n_open;
+  finfo.frags_closed = hc[mhm::UFRAG_C_CLOSED];
+  finfo.local_cycles = hc[mhm::UFRAG_C_CYCLES];
+  finfo.cross_links = hc[mhm::UFRAG_C_LINKS];
+  const int t2 = mark();
+
+  // 3. the open fragments' records, on every rank
+  if ((rc = gather(&n_open, 1))) return rc;
+  std::vector<uint64_t> fbase((size_t)g + 1, 0);
+  for (int r = 0; r < g; r++) fbase[(size_t)r + 1] = fbase[(size_t)r] + all[2 * (size_t)r];
+  const uint64_t NF = fbase[(size_t)g], f0 = fbase[(size_t)me];
+  if (NF >= 0xffffffffull)
+    return fail(MHMKC_EUNSUPPORTED, "uutigs_frags: %llu open fragments on all ranks, at most 2^32-2", (unsigned long long)NF);
+  finfo.frags_open_all = NF;
+  const size_t rec_kb = 8 * (size_t)nl, rec_rb = 8 * (size_t)mhm::UFRAG_REST_WORDS;
+  if (NF) {
+    hfail(grow(d_uf[UF_KEYS], NF * rec_kb + 64), "fragment keys");
+    if (!lrc) hfail(grow(d_uf[UF_REST], NF * rec_rb + 64), "fragment records");
+  }
+  uint64_t *fkeys = d_uf[UF_KEYS].as<uint64_t>(), *frest = d_uf[UF_REST].as<uint64_t>();
+  if (!lrc && n_open &&
+      ((e = mhm::launch_ufrag_emit(out_rows(), n, nl, nlo, starts, n_frag, RF, xlink, rrow, rrank, rstat, lf_open, me, n_open,
+                                   fkeys + f0 * nl, frest + f0 * mhm::UFRAG_REST_WORDS, stream)) != hipSuccess ||
+       (e = hipStreamSynchronize(stream)) != hipSuccess))
+    hfail(e, "fragment records");
+  if ((rc = gather(nullptr, 0))) return rc;
+  if (NF) {
+    snd.clear();
+    rcv.clear();
+    for (int p = 0; p < g; p++) {
+      if (p == me) continue;
+      const uint64_t np = fbase[(size_t)p + 1] - fbase[(size_t)p];
+      if (n_open) {
+        snd.push_back({p, fkeys + f0 * nl, n_open * rec_kb});
+        snd.push_back({p, frest + f0 * mhm::UFRAG_REST_WORDS, n_open * rec_rb});
+      }
+      if (np) {
+        rcv.push_back({p, fkeys + fbase[(size_t)p] * nl, np * rec_kb});
+        rcv.push_back({p, frest + fbase[(size_t)p] * mhm::UFRAG_REST_WORDS, np * rec_rb});
+      }
+    }
+    if ((rc = quiet_move(snd, rcv))) return rc;
+    moved(MHMKC_UFRAGS_GATHER, n_open * (uint64_t)(g - 1), NF - n_open, n_open * (uint64_t)(g - 1) * (rec_kb + rec_rb),
+          (NF - n_open) * (rec_kb + rec_rb));
+  }
+  const int t3 = mark();
+
+  // 4. the fragment graph, ranked on this rank: per-fragment results comp, off, isstart, cidx, seg_pos, flag
+  const size_t m4 = align_up((NF + 1) * 4, 256), m8 = align_up((NF + 1) * 8, 256);
+  const size_t work_b = std::max(mhm::ufrag_resolve_scratch_bytes(NF), mhm::ufrag_segs_scratch_bytes(NF));
+  const size_t tmp_b = mhm::ufrag_tmp_bytes(std::max(2 * NF, n) + 1);
+  mhm::UfragGraph fg{};
+  uint64_t *fentry = nullptr, *seg_pos = nullptr;
+  uint32_t *fcomp = nullptr, *foff = nullptr, *fis = nullptr, *fcidx = nullptr;
+  uint8_t *fflag = nullptr;
+  mhm::UutigPort *FF = nullptr, *FG = nullptr;
+  uint64_t XC = 0;
+  std::vector<uint32_t> cbase((size_t)g + 1, 0);
+  hfail(grow(d_uf[UF_TMP], tmp_b), "sort scratch");
+  if (!lrc && NF) {
+    if ((e = grow(d_uf[UF_ENT], 2 * NF * 8 + 64)) != hipSuccess ||
+        (e = grow(d_uf[UF_FA], 2 * NF * sizeof(mhm::UutigPort))) != hipSuccess ||
+        (e = grow(d_uf[UF_FB], 2 * NF * sizeof(mhm::UutigPort))) != hipSuccess ||
+        (e = grow(d_uf[UF_META], 4 * m4 + m8 + NF + 64)) != hipSuccess || (e = grow(d_uf[UF_WORK], work_b)) != hipSuccess)
+      hfail(e, "fragment ranking scratch");
+  }
+  if (!lrc && NF) {
+    fentry = d_uf[UF_ENT].as<uint64_t>();
+    char *mb = d_uf[UF_META].as<char>();
+    fcomp = (uint32_t *)mb;
+    foff = (uint32_t *)(mb + m4);
+    fis = (uint32_t *)(mb + 2 * m4);
+    fcidx = (uint32_t *)(mb + 3 * m4);
+    seg_pos = (uint64_t *)(mb + 4 * m4);
+    fflag = (uint8_t *)(mb + 4 * m4 + m8);
+    FF = d_uf[UF_FA].as<mhm::UutigPort>();
+    FG = d_uf[UF_FB].as<mhm::UutigPort>();
+    const int fnl = nl;
+    if ((e = mhm::launch_ufrag_resolve(frest, NF, d_uf[UF_WORK].p, work_b, d_uf[UF_TMP].p, tmp_b, fentry, stream)) != hipSuccess)
+      hfail(e, "fragment links");
+    if (!lrc)
+      lfail(rank_ports(NF, fkeys, nl, nl,
+                       [&, fnl](const uint64_t *list, uint64_t n_items, const mhm::UutigPort *cut, uint32_t round,
+                                mhm::UutigPort *s) {
+                         return mhm::launch_ufrag_init(fkeys, frest, NF, fnl, fentry, list, n_items, cut, round, s, stream);
+                       },
+                       FF, FG, ctr + mhm::UFRAG_C_ACTIVE, d_uf[UF_FLIST], finfo.rounds_frags, finfo.cycle_rounds_frags));
+    if (!lrc) {
+      if ((e = mhm::launch_ufrag_place(fkeys, NF, nl, FF, fentry, fcomp, foff, fflag, fis, fcidx, d_uf[UF_TMP].p, tmp_b, ctr,
+                                       stream)) != hipSuccess ||
+          (e = mhm::launch_ufrag_owned(frest, f0, fbase[(size_t)me + 1], NF, fflag, n, cstarts, ctr, stream)) != hipSuccess)
+        hfail(e, "fragment places");
+      for (int r = 0; r <= g && !lrc; r++)
+        if ((e = hipMemcpyAsync(&cbase[(size_t)r], fcidx + fbase[(size_t)r], 4, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+          hfail(e, "contig places");
+      if (!lrc && (e = counters()) != hipSuccess) hfail(e, "fragment places");
+      if (!lrc && hc[mhm::UFRAG_C_BAD]) lfail(fail(MHMKC_EHIP, "uutigs_frags: a fragment's contig lies outside the fragments"));
+      if (!lrc) XC = cbase[(size_t)g];
+      if (!lrc && hc[mhm::UFRAG_C_MINE] != (uint64_t)(cbase[(size_t)me + 1] - cbase[(size_t)me]))
+        lfail(fail(MHMKC_EHIP, "uutigs_frags: the rank's cross-rank contigs do not add up"));
+    }
+  }
+  const uint64_t n_mine = lrc ? 0 : hc[mhm::UFRAG_C_STARTS];
+  if (!lrc && n_mine > n) lfail(fail(MHMKC_EHIP, "uutigs_frags: %llu contigs in %llu rows", (unsigned long long)n_mine,
+                                     (unsigned long long)n));
+  finfo.ctgs_cross_all = XC;
+  finfo.ctgs_cross_mine = hc[mhm::UFRAG_C_MINE];
+  finfo.cycles_cross_all = hc[mhm::UFRAG_C_XCYCLES];
+  const int t4 = mark();
+
+  // 5. the contigs: counts and first ids, this rank's table, the cross-rank contigs' ids
+  const uint64_t cnts[3] = {n_mine, XC, hc[mhm::UFRAG_C_XCYCLES]};
+  if ((rc = gather(cnts, 3))) return rc;
+  uint64_t first_id = 0, n_all = 0;
+  for (int r = 0; r < g; r++) {
+    if (all[4 * (size_t)r + 1] != XC || all[4 * (size_t)r + 2] != cnts[2])
+      return fail(MHMKC_ETRANSPORT, "uutigs_frags: rank %d ranked the fragment graph differently", r);
+    if (r < me) first_id += all[4 * (size_t)r];
+    n_all += all[4 * (size_t)r];
+  }
+  if (n_all >= 0xffffffffull)
+    return fail(MHMKC_EUNSUPPORTED, "uutigs_frags: %llu contigs on all ranks, at most 2^32-2", (unsigned long long)n_all);
+  const size_t off_b = align_up((n_mine + 1) * 8, 256), dep_b = align_up(n_mine * 8 + 8, 256);
+  const size_t tbl_b = mhm::ufrag_table_scratch_bytes(n_mine);
+  uint64_t n_bases = 0;
+  u_nctgs = n_mine;  // (u_depths / u_nkmers address by it)
+  hfail(grow(d_uctg, off_b + dep_b + n_mine * 4 + 64), "contig table");
+  if (!lrc) hfail(grow(d_uf[UF_TBL], tbl_b + 64), "contig table scratch");
+  if (!lrc && XC) hfail(grow(d_uf[UF_GID], XC * 4 + 64), "contig ids");
+  uint32_t *xgid = d_uf[UF_GID].as<uint32_t>();
+  fg = mhm::UfragGraph{fkeys, frest, lrc ? 0 : NF, nl, fentry, FF, fcomp, foff, fflag, fcidx, xgid, XC};
+  uint64_t *offsets = d_uctg.as<uint64_t>();
+  std::vector<unsigned long long> glen((size_t)g * g, 0), gstart((size_t)g * g + 1, 0);
+  std::vector<uint64_t> rbase((size_t)g, 0), broff((size_t)g, 0);
+  uint64_t b_send = 0, b_recv = 0, b_all = 0, seg_base = 0;
+  if (!lrc) {
+    if ((e = mhm::launch_ufrag_table(out_rows(), n, k, nl, nlo, cstarts, n_mine, RF, row_ctg, lf_open, lf_ctg, n_frag, f0, n_open,
+                                     fg, first_id, xgid, d_uf[UF_TBL].p, tbl_b, d_uf[UF_TMP].p, tmp_b, (uint32_t *)u_nkmers(),
+                                     (double *)u_depths(), offsets, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(&n_bases, offsets + n_mine, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (NF && (e = mhm::launch_ufrag_segs(fg, k, g, d_uf[UF_WORK].p, work_b, d_uf[UF_TMP].p, tmp_b, seg_pos, d_glen, stream)) !=
+                   hipSuccess) ||
+        (e = hipMemcpyAsync(glen.data(), d_glen, 8 * (size_t)g * g, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream)) != hipSuccess)
+      hfail(e, "contig table");
+  }
+  if (!lrc) {
+    // the segment layout, grouped by (sender, owner) in that order: what seg_pos counts in
+    for (size_t x = 0; x < (size_t)g * g; x++) gstart[x + 1] = gstart[x] + glen[x];
+    b_all = gstart[(size_t)g * g];
+    seg_base = gstart[(size_t)me * g];
+    b_send = gstart[(size_t)(me + 1) * g] - seg_base;
+    for (int r = 0; r < g; r++) {
+      if (r == me) continue;
+      broff[(size_t)r] = b_recv;
+      rbase[(size_t)r] = b_recv - gstart[(size_t)r * g + me];  // (mod 2^64)
+      b_recv += glen[(size_t)r * g + me];
+    }
+    if (glen[(size_t)me * g + me]) lfail(fail(MHMKC_EHIP, "uutigs_frags: a rank sends itself bases"));
+    if (!lrc && b_recv > n_bases) lfail(fail(MHMKC_EHIP, "uutigs_frags: %llu bases arrive for %llu", (unsigned long long)b_recv,
+                                             (unsigned long long)n_bases));
+    if (!lrc && n_bases) hfail(grow(d_useq, n_bases), "bases");
+    if (!lrc && b_send) hfail(grow(d_uf[UF_BSEND], b_send + 64), "bases to send");
+    if (!lrc && b_recv) hfail(grow(d_uf[UF_BRECV], b_recv + 64), "bases to receive");
+    if (!lrc && (e = hipMemcpyAsync(d_rbase, rbase.data(), 8 * (size_t)g, hipMemcpyHostToDevice, stream)) != hipSuccess)
+      hfail(e, "segment places");
+  }
+  if (!lrc) u_nbases = n_bases;
+  if ((rc = gather(&b_all, 1))) return rc;
+  for (int r = 0; r < g; r++)
+    if (all[2 * (size_t)r] != b_all)
+      return fail(MHMKC_ETRANSPORT, "uutigs_frags: rank %d lays the segments out differently", r);
+  if (XC) {
+    snd.clear();
+    rcv.clear();
+    const uint64_t mine_x = cbase[(size_t)me + 1] - cbase[(size_t)me];
+    for (int p = 0; p < g; p++) {
+      if (p == me) continue;
+      const uint64_t px = cbase[(size_t)p + 1] - cbase[(size_t)p];
+      if (mine_x) snd.push_back({p, xgid + cbase[(size_t)me], mine_x * 4});
+      if (px) rcv.push_back({p, xgid + cbase[(size_t)p], px * 4});
+    }
+    if ((rc = quiet_move(snd, rcv))) return rc;
+    moved(MHMKC_UFRAGS_IDS, mine_x * (uint64_t)(g - 1), XC - mine_x, mine_x * (uint64_t)(g - 1) * 4, (XC - mine_x) * 4);
+  }
+  const int t5 = mark();
+
+  // 6. every own row's final place and bases; the segments to their owners
+  if (n && ((e = mhm::launch_ufrag_rows(out_rows(), n, k, nl, nlo, row_ctg, row_pos, row_rc, lf_open, lf_ctg, n_frag, f0, n_open,
+                                        fg, me, first_id, n_mine, offsets, u_nkmers(), n_bases, d_useq.as<char>(), seg_pos,
+                                        seg_base, b_send, d_uf[UF_BSEND].as<char>(), stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(stream)) != hipSuccess))
+    hfail(e, "rows");
+  if ((rc = gather(nullptr, 0))) return rc;
+  if (b_all) {
+    snd.clear();
+    rcv.clear();
+    for (int p = 0; p < g; p++) {
+      if (p == me) continue;
+      if (glen[(size_t)me * g + p])
+        snd.push_back({p, d_uf[UF_BSEND].as<char>() + (gstart[(size_t)me * g + p] - seg_base), glen[(size_t)me * g + p]});
+      if (glen[(size_t)p * g + me]) rcv.push_back({p, d_uf[UF_BRECV].as<char>() + broff[(size_t)p], glen[(size_t)p * g + me]});
+    }
+    if ((rc = quiet_move(snd, rcv))) return rc;
+    moved(MHMKC_UFRAGS_BASES, b_send, b_recv, b_send, b_recv);
+    if (b_recv &&
+        (e = mhm::launch_ufrag_scatter(fg, k, me, g, first_id, n_mine, offsets, n_bases, d_useq.as<char>(), seg_pos,
+                                       (const uint64_t *)d_rbase, d_uf[UF_BRECV].as<char>(), b_recv, stream)) != hipSuccess)
+      hfail(e, "received bases");
+  }
+  const int t6 = mark();
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) hfail(e, "uutigs_frags");
+  if ((rc = gather(nullptr, 0))) return rc;
+
+  ur_first = first_id;
+  ur_all = n_all;
+  finfo.n_ctgs = n_mine;
+  finfo.n_bases = n_bases;
+  finfo.first_id = first_id;
+  finfo.n_ctgs_all = n_all;
+  const int marks[MHMKC_UFRAGS_STAGES + 1] = {t0, t1, t2, t3, t4, t5, t6};
+  for (int i = 0; i < MHMKC_UFRAGS_STAGES; i++) finfo.ms_stage[i] = ms(marks[i], marks[i + 1]);
+  finfo.ms_total = ms(t0, t6);
+  for (const DevBuf &b : d_uf) finfo.scratch_bytes += b.cap;
+  finfo.kept_bytes = d_uctg.cap + d_useq.cap + d_urows.cap;
+  return MHMKC_OK;
+}
+
+int mhmkc::uutigs_frags() {
+  if (uranks_ready) return MHMKC_OK;
+  finfo = mhmkc_uutig_frags_info{};
+  uinfo = mhmkc_uutig_info{};
+  if (!rlinks_ready) {  // (a collective of its own: every rank of a finished round is in the same state)
+    const int rc = dbjg_links_ranks();
+    if (rc) return rc;
+    finfo.links_built = 1;
+  }
+  drop_query();  // this rank's index and single-rank links are not needed: the routed links stay
+  std::vector<hipEvent_t> evs;
+  const int rc = uutigs_frags_build(evs);
+  (void)hipStreamSynchronize(stream);
+  for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+  drop_ufrags_scratch();
+  urinfo = mhmkc_uutig_ranks_info{};
+  if (rc) {
+    d_uctg.release();
+    d_useq.release();
+    d_urows.release();
+    u_nctgs = u_nbases = ur_first = ur_all = 0;
+    uutigs_ready = false;
+  } else {
+    uutigs_ready = uranks_ready = ufrags_built = true;
+    urinfo.n_ctgs = uinfo.n_ctgs = u_nctgs;
+    urinfo.n_bases = uinfo.n_bases = u_nbases;
+    urinfo.first_id = ur_first;
+    urinfo.n_ctgs_all = ur_all;
+    urinfo.n_rows = finfo.n_rows;
+    urinfo.n_rows_all = finfo.n_rows_all;
+    urinfo.kept_bytes = uinfo.kept_bytes = finfo.kept_bytes;
+    uinfo.scratch_bytes = finfo.scratch_bytes;
+  }
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  return rc;
+}
+
 static int uutigs_need(mhmkc_t h) {
   if (!h) return MHMKC_EINVAL;
   if (h->cfg.n_ranks > 1 && !h->uranks_ready) return h->fail(MHMKC_EUNSUPPORTED, "uutigs: single-rank handles only");
@@ -5078,6 +5645,41 @@ int mhmkc_uutigs_ranks(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases, uint64_t 
 int mhmkc_uutigs_ranks_info(mhmkc_t h, mhmkc_uutig_ranks_info *info) {
   if (!h || !info) return MHMKC_EINVAL;
   *info = h->urinfo;
+  return MHMKC_OK;
+}
+
+static int route_need(mhmkc_t h, const char *what);
+
+int mhmkc_uutigs_frags(mhmkc_t h, uint64_t *n_ctgs, uint64_t *n_bases, uint64_t *first_id, uint64_t *n_ctgs_all) {
+  if (!h) return MHMKC_EINVAL;
+  if (h->cfg.n_ranks <= 1) {  // one rank: mhmkc_uutigs, as mhmkc_uutigs_ranks gives it
+    int rc = mhmkc_uutigs_ranks(h, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+  } else {
+    int rc = route_need(h, "uutigs_frags");
+    if (rc) return rc;
+    if ((rc = h->uutigs_frags())) return rc;
+  }
+  if (!h->ufrags_built) {  // no fragment build behind the kept state: the seven fields the two infos share
+    h->finfo = mhmkc_uutig_frags_info{};
+    h->finfo.n_ctgs = h->u_nctgs;
+    h->finfo.n_bases = h->u_nbases;
+    h->finfo.first_id = h->ur_first;
+    h->finfo.n_ctgs_all = h->ur_all;
+    h->finfo.n_rows = h->urinfo.n_rows;
+    h->finfo.n_rows_all = h->urinfo.n_rows_all;
+    h->finfo.kept_bytes = h->urinfo.kept_bytes;
+  }
+  if (n_ctgs) *n_ctgs = h->u_nctgs;
+  if (n_bases) *n_bases = h->u_nbases;
+  if (first_id) *first_id = h->ur_first;
+  if (n_ctgs_all) *n_ctgs_all = h->ur_all;
+  return MHMKC_OK;
+}
+
+int mhmkc_uutigs_frags_info(mhmkc_t h, mhmkc_uutig_frags_info *info) {
+  if (!h || !info) return MHMKC_EINVAL;
+  *info = h->finfo;
   return MHMKC_OK;
 }
 

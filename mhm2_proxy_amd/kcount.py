@@ -636,6 +636,24 @@ class KmerCounter:
         self._check(N.lib().mhmkc_uutigs_ranks_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    # -- the same uutigs from rank-local fragments (mhmkc_uutigs_frags)
+    def uutigs_frags(self) -> dict:
+        """uutigs_ranks() by the fragment build (mhmkc_uutigs_frags): every rank ranks its own rows, the open
+        fragments of all ranks are joined in a replicated fragment graph, and only they and the bases of contigs owned
+        elsewhere travel. Collective over the ranks of a finished MHMKC_OWNER_MINIMIZER counter; the same contigs, ids and
+        row map, and the same kept state: whichever of the two runs first after a finish builds, the other then returns it.
+        Returns {"n_ctgs", "n_bases", "first_id", "n_ctgs_all"}."""
+        nc, nb, fi, na = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(N.lib().mhmkc_uutigs_frags(self._h, C.byref(nc), C.byref(nb), C.byref(fi), C.byref(na)))
+        return {"n_ctgs": int(nc.value), "n_bases": int(nb.value), "first_id": int(fi.value), "n_ctgs_all": int(na.value)}
+
+    def uutigs_frags_info(self) -> dict:
+        """Fragment and contig counts, rounds, records and bytes moved per stage, stage times (device events) and memory of
+        the last uutigs_frags build (mhmkc_uutigs_frags_info)."""
+        info = N.MhmkcUutigFragsInfo()
+        self._check(N.lib().mhmkc_uutigs_frags_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     # -- queries answered by the owner rank (mhmkc_lookup_ranks, mhmkc_dbjg_links_ranks)
     def lookup_ranks(self, keys, canonicalize: bool = False):
         """lookup() for k-mers that may live on any rank (mhmkc_lookup_ranks; get_kmer_target_rank + the rpc of
