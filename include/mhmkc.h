@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-/* (14 gained symbols without a new number: mhmkc_uutigs_frags, mhmkc_uutigs_frags_info) */
+/* (14 gained symbols without a new number: mhmkc_uutigs_frags, mhmkc_uutigs_frags_info; then mhmkc_ctgs_stats_device,
+ * mhmkc_uutigs_stats, mhmkc_ctgs_fasta_device, mhmkc_uutigs_fasta, mhmkc_fasta_device, mhmkc_fasta_fetch,
+ * mhmkc_fasta_write, mhmkc_fasta_info and the code MHMKC_EIO) */
 #define MHMKC_ABI_VERSION 14
 #define MHMKC_COMM_ID_BYTES 128
 
@@ -50,7 +52,8 @@ enum {
   MHMKC_ESTATE = -5,      /* call out of order (e.g. fetch before finish) */
   MHMKC_EBADCHAR = -6,    /* input byte outside the PackedRead code range (reference DIE, kcount_cpu.cpp:453-458) */
   MHMKC_EUNSUPPORTED = -7, /* valid for the reference but not supported here */
-  MHMKC_ETRANSPORT = -8    /* a mhmkc_set_transport callback failed, or none was set where needed */
+  MHMKC_ETRANSPORT = -8,   /* a mhmkc_set_transport callback failed, or none was set where needed */
+  MHMKC_EIO = -9           /* mhmkc_fasta_write: the file could not be created, sized, opened or written */
 };
 
 typedef struct mhmkc *mhmkc_t;
@@ -653,6 +656,82 @@ typedef struct {
   uint64_t kept_bytes;      /* what stays on the device: the links of mhmkc_dbjg_links_ranks, else 0 */
 } mhmkc_route_info_t;
 int mhmkc_route_info(mhmkc_t h, mhmkc_route_info_t *info);
+
+/* Assembly statistics and FASTA output from device-resident contigs: what the reference does with its
+ * Contigs at the end of every contigging round and of the run, Contigs::print_stats (src/contigs.cpp:92-164;
+ * src/contigging.cpp:152, src/main.cpp:216) and Contigs::dump_contigs (src/contigs.cpp:166-180; src/contigging.cpp:147-150,
+ * src/main.cpp:213), without the contigs leaving the device as objects.
+ *
+ * The figures of print_stats over the contigs with len >= min_ctg_len. Integers are exact. tot_depth is a floating sum in
+ * a fixed order (chunks of 1024 contigs: four per lane in index order, a tree over 256 lanes, the chunks in order), so it
+ * depends on the inputs alone; all.tot_depth is the ranks' mine.tot_depth added in rank order. n50 / l50 (not printed by
+ * the reference, whose approximate N50 is commented out, src/contigs.cpp:114-143): with the counted lengths in descending
+ * order, l50 is the smallest number of leading contigs whose lengths sum to s with 2 s >= tot_len, n50 the length of the
+ * last of them; both 0 when nothing is counted. */
+typedef struct {
+  uint64_t n_ctgs, tot_len, max_len, n_ns; /* contigs with len >= min_ctg_len; n_ns: bytes equal to 'N' in them */
+  double tot_depth;                        /* sum of their depths; the reference prints tot_depth / n_ctgs */
+  uint64_t len_sums[5];                    /* bases in contigs of len >= 1000, 5000, 10000, 25000, 50000 (contigs.cpp:96,108-110) */
+  uint64_t n50, l50;
+} mhmkc_ctg_stats;
+
+/* d_seqs, d_seq_offsets (n_ctgs + 1 entries, the first 0, never falling), d_depths (double): device arrays of the shapes
+ * mhmkc_add_ctgs_device takes, read during the call only, on the handle's stream (mhmkc_wait_stream first when another
+ * stream wrote them). With n_ctgs == 0 the pointers may be NULL. The handle may be in any state. mine: this rank's
+ * contigs; all: the reduction over the ranks of the handle (reduce_one of contigs.cpp:144-148,162, here returned on every
+ * rank), n50 / l50 exact over all ranks' contigs (each rank's counted lengths travel as 4 bytes each). Either may be NULL.
+ * n_ranks > 1: collective over RCCL or mhmkc_set_transport; a failure on one rank is a failure on all (MHMKC_ETRANSPORT on
+ * the others). One rank: all == mine. MHMKC_EINVAL: offsets that do not start at 0 or fall (the message names the first
+ * such contig); MHMKC_EUNSUPPORTED: a counted contig of 2^32 bases or more. The call's device scratch (16 bytes per contig)
+ * is freed before it returns. */
+int mhmkc_ctgs_stats_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const double *d_depths,
+                            uint64_t n_ctgs, uint32_t min_ctg_len, mhmkc_ctg_stats *mine, mhmkc_ctg_stats *all);
+/* The same of the handle's uutigs (mhmkc_uutigs_device). One rank: built first if needed. n_ranks > 1: after
+ * mhmkc_uutigs_ranks / mhmkc_uutigs_frags, else MHMKC_EUNSUPPORTED before any collective, as the other getters. */
+int mhmkc_uutigs_stats(mhmkc_t h, uint32_t min_ctg_len, mhmkc_ctg_stats *mine, mhmkc_ctg_stats *all);
+
+/* The text dump_contigs writes, built on the device and kept there: for every contig c with len >= min_ctg_len, in order,
+ * ">Contig" + to_string(int64 id) + " " + to_string(double depth) + "\n" + seq + "\n" with id = first_id + c, c the index
+ * in the unfiltered list. The sequence is written as it is (contigs.cpp:173-176 computes the canonical strand and then
+ * writes ctg->seq); no line wrapping. to_string(double) is "%f": six decimals, correctly rounded, ties to even, done in
+ * integers on the device.
+ * Supported: depths finite with the sign bit clear and < 2^32 (only contigs that are written are checked);
+ * first_id + n_ctgs <= 2^63 - 1; offsets as above. Else MHMKC_EINVAL, the message names the first offending contig, found
+ * on the device before a byte is written. *n_bytes: this rank's text; *file_offset: the sum of the lower ranks' n_bytes
+ * (dist_ofstream's prefix sum, upcxx-utils/src/ofstream.cpp:184,454); *n_bytes_all: the file's size. Any may be NULL.
+ * n_ranks > 1: collective (one 16-byte all-gather: status and size); a failure on one rank is a failure on all
+ * (MHMKC_ETRANSPORT on the others) and leaves no text.
+ * The text stays on the device, one at a time: the next fasta call replaces it, mhmkc_reset, mhmkc_finish and
+ * mhmkc_destroy free it; it is counted in mhmkc_stats.device_bytes[_peak]. The scratch (16 bytes per contig) is freed
+ * before the call returns. */
+int mhmkc_ctgs_fasta_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const double *d_depths,
+                            uint64_t n_ctgs, uint64_t first_id, uint32_t min_ctg_len, uint64_t *n_bytes,
+                            uint64_t *file_offset, uint64_t *n_bytes_all);
+/* The same of the handle's uutigs with the first_id of the ranks build (0 on one rank); state rules of mhmkc_uutigs_stats. */
+int mhmkc_uutigs_fasta(mhmkc_t h, uint32_t min_ctg_len, uint64_t *n_bytes, uint64_t *file_offset, uint64_t *n_bytes_all);
+/* The kept text (NULL when it is empty). Without one: MHMKC_ESTATE. */
+int mhmkc_fasta_device(mhmkc_t h, const char **d_text, uint64_t *n_bytes);
+/* Copy it to text[n_bytes] (host). */
+int mhmkc_fasta_fetch(mhmkc_t h, char *text);
+/* Write it to the file at `path`, at file_offset: chunks of fasta_chunk_bytes (mhmkc_debug_set; default 4 MiB, at least
+ * 64) are copied into two pinned buffers in turn, chunk c + 1 on the wire while chunk c is written with pwrite.
+ * One rank: the file is created, truncated and written. n_ranks > 1: collective. Rank 0 creates and truncates the file
+ * and sets its length to n_bytes_all; the ranks exchange their status (which is the barrier); every rank with bytes opens
+ * the file and writes its block; the ranks exchange their status again. A rank without bytes opens nothing. All ranks
+ * must see the same file under `path` (one node, or a shared file system). Offsets are 64-bit. MHMKC_EIO with the
+ * errno text on the rank that failed, MHMKC_ETRANSPORT on the others. */
+int mhmkc_fasta_write(mhmkc_t h, const char *path);
+/* How the last fasta build and the last mhmkc_fasta_write went. Every field is a uint64_t or a double. */
+typedef struct {
+  uint64_t n_ctgs, n_written;   /* contigs given; of them in the text */
+  uint64_t n_bytes, file_offset, n_bytes_all;
+  uint64_t text_bytes;          /* device memory of the kept text */
+  uint64_t scratch_bytes;       /* the build's device scratch */
+  double ms_table, ms_copy, ms_headers, ms_total; /* device events: checks + lengths + scan; bases; headers */
+  uint64_t write_chunks;        /* chunks of the last mhmkc_fasta_write */
+  double ms_write;              /* its wall time, status exchanges included */
+} mhmkc_fasta_info_t;
+int mhmkc_fasta_info(mhmkc_t h, mhmkc_fasta_info_t *info);
 
 /* Host-staged exchange between ranks (instead of RCCL): for n_ranks > 1 with comm_id == NULL, set before
  * the first mhmkc_finish. Every rank's callbacks are called collectively, in the same order on all ranks, with

@@ -49,7 +49,9 @@ extern "C" {
  *                 that a lane converts several 16-byte vectors in turn on a small batch (0: the launch's own grid)
  *   ctgx_grid     at most v workgroups for the kernels of the multi-rank device gather of contigs (kcount_ctgx.hip:
  *                 k_ctgx_lens, k_ctgx_pack, k_ctgx_windows), so that their grid-stride loops turn several times on a
- *                 small set (0: the launches' own grids) */
+ *                 small set (0: the launches' own grids)
+ *   fasta_chunk_bytes  the chunk of mhmkc_fasta_write's device-to-host copies and pwrites (0: 4 MiB; at least 64, else
+ *                 MHMKC_EINVAL), so that chunk edges fall anywhere in a small text */
 int mhmkc_debug_set(const char *knob, int64_t value);
 /* Every knob back to its default. */
 void mhmkc_debug_reset(void);

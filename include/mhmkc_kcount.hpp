@@ -32,6 +32,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <iostream>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -761,6 +762,99 @@ struct Contig {
 using Contigs = std::vector<Contig>;
 
 // ---------------------------------------------------------------------------------------------
+// Contigs::print_stats / Contigs::dump_contigs (src/contigs.cpp:92-180)
+
+// What upcxx_utils' perc_str gives (upcxx-utils/src/log.cpp:428-434): the number, then its share of the total in per
+// cent with two decimals in parentheses; an empty total counts as 0 %
+inline std::string perc_str(int64_t num, int64_t tot) {
+  char buf[64];
+  std::snprintf(buf, sizeof buf, "%lld (%.2f%%)", (long long)num, tot ? 100.0 * (double)num / (double)tot : 0.0);
+  return buf;
+}
+
+// The block print_stats logs (contigs.cpp:151-163), line for line and without the colour codes, from the figures of
+// mhmkc_uutigs_stats / mhmkc_ctgs_stats_device (`all`) or of ctg_stats below. A double is printed as the stream prints
+// it at its default precision ("%g"); the class label is left-justified in 19 columns
+inline std::string assembly_stats_text(const mhmkc_ctg_stats &st, unsigned min_ctg_len) {
+  static const unsigned kbp[5] = {1, 5, 10, 25, 50};
+  const long long n = (long long)st.n_ctgs, tot = (long long)st.tot_len, ns = (long long)st.n_ns;
+  char buf[160];
+  std::string out;
+  auto line = [&](const char *fmt, auto... v) {
+    std::snprintf(buf, sizeof buf, fmt, v...);
+    out += buf;
+  };
+  line("Assembly statistics (contig lengths >= %u)\n", min_ctg_len);
+  line("    Number of contigs:       %lld\n", n);
+  line("    Total assembled length:  %lld\n", tot);
+  line("    Average contig depth:    %g\n", st.tot_depth / (double)n);
+  line("    Number of Ns/100kbp:     %g (%lld)\n", (double)ns * 100000.0 / (double)tot, ns);
+  line("    Max. contig length:      %lld\n", (long long)st.max_len);
+  out += "    Contig lengths:\n";
+  for (int i = 0; i < 5; i++) {
+    const std::string label = std::to_string(kbp[i]) + "kbp:";
+    line("        > %-19s%s\n", label.c_str(), perc_str((int64_t)st.len_sums[i], tot).c_str());
+  }
+  return out;
+}
+
+// print_stats' figures of a host Contigs vector (the loop of contigs.cpp:101-113), with the N50 / L50 of mhmkc.h
+inline mhmkc_ctg_stats ctg_stats(const Contigs &ctgs, unsigned min_ctg_len) {
+  static const uint64_t cls[5] = {1000, 5000, 10000, 25000, 50000};
+  mhmkc_ctg_stats st{};
+  std::vector<uint64_t> lens;
+  lens.reserve(ctgs.size());
+  for (const Contig &ctg : ctgs) {
+    const uint64_t len = ctg.seq.length();
+    if (len < min_ctg_len) continue;
+    st.n_ctgs++;
+    st.tot_len += len;
+    st.tot_depth += ctg.depth;
+    st.max_len = std::max<uint64_t>(st.max_len, len);
+    for (int i = 0; i < 5; i++)
+      if (len >= cls[i]) st.len_sums[i] += len;
+    st.n_ns += (uint64_t)std::count(ctg.seq.begin(), ctg.seq.end(), 'N');
+    lens.push_back(len);
+  }
+  std::sort(lens.rbegin(), lens.rend());
+  uint64_t s = 0;
+  for (size_t i = 0; i < lens.size(); i++) {
+    s += lens[i];
+    if (2 * s >= st.tot_len) {
+      st.n50 = lens[i];
+      st.l50 = i + 1;
+      break;
+    }
+  }
+  return st;
+}
+
+inline void print_stats(const Contigs &ctgs, unsigned min_ctg_len, std::ostream &out = std::cout) {
+  out << assembly_stats_text(ctg_stats(ctgs, min_ctg_len), min_ctg_len);
+}
+
+// dump_contigs at one rank (contigs.cpp:166-180): per contig of at least min_ctg_len bases a header line with the id
+// and the depth as to_string gives them, then the sequence as it is on one line
+inline void dump_contigs(const Contigs &ctgs, const std::string &fname, unsigned min_ctg_len) {
+  std::ofstream of(fname, std::ios::binary | std::ios::trunc);
+  if (!of) die("dump_contigs: cannot open " + fname);
+  std::string rec;
+  for (const Contig &ctg : ctgs) {
+    if (ctg.seq.size() < min_ctg_len) continue;
+    rec.assign(">Contig");
+    rec += std::to_string(ctg.id);
+    rec += ' ';
+    rec += std::to_string(ctg.depth);
+    rec += '\n';
+    rec += ctg.seq;
+    rec += '\n';
+    of.write(rec.data(), (std::streamsize)rec.size());
+  }
+  of.close();
+  if (!of) die("dump_contigs: writing " + fname + " failed");
+}
+
+// ---------------------------------------------------------------------------------------------
 // HashTableInserter / KmerDHT / SeqBlockInserter
 
 // Where this rank sits. n_ranks > 1: the exchange runs over RCCL (comm_id from mhmkc_comm_id on rank 0,
@@ -1041,6 +1135,23 @@ class HashTableInserter {
     out.reserve(n_ctgs);
     for (uint64_t c = 0; c < n_ctgs; c++)
       out.push_back(Contig{(int64_t)c, std::string(seqs.data() + offs[c], seqs.data() + offs[c + 1]), depths[c]});
+  }
+  // print_stats' figures of the uutigs over all ranks (mhmkc_uutigs_stats: ctgs.print_stats(500) of a contigging round,
+  // src/contigging.cpp:152), computed on the device; assembly_stats_text gives the logged block. Collective with
+  // n_ranks > 1, after mhmkc_uutigs_ranks / mhmkc_uutigs_frags
+  mhmkc_ctg_stats uutigs_stats(unsigned min_ctg_len, mhmkc_ctg_stats *mine = nullptr) {
+    mhmkc_ctg_stats all{};
+    check(mhmkc_uutigs_stats(h_, min_ctg_len, mine, &all), h_, "mhmkc_uutigs_stats");
+    return all;
+  }
+  // ctgs.dump_contigs(fname, min_ctg_len) of the uutigs (src/contigging.cpp:147-150, src/main.cpp:213): the text is built
+  // on the device and written by every rank at its offset of the one file (mhmkc_uutigs_fasta, mhmkc_fasta_write); all
+  // ranks must see the same file. Returns the file's size
+  uint64_t dump_uutigs(const std::string &fname, unsigned min_ctg_len) {
+    uint64_t n_all = 0;
+    check(mhmkc_uutigs_fasta(h_, min_ctg_len, nullptr, nullptr, &n_all), h_, "mhmkc_uutigs_fasta");
+    check(mhmkc_fasta_write(h_, fname.c_str()), h_, "mhmkc_fasta_write");
+    return n_all;
   }
 };
 

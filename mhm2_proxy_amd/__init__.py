@@ -13,6 +13,7 @@ from .kcount import (  # noqa: F401
     SharedGpuCounter,
     TorchDistTransport,
     analyze_kmers,
+    assembly_stats_text,
     comm_id,
     get_kmer_target_rank,
     kmer_from_string,
@@ -28,5 +29,5 @@ __all__ = [
     "KmerCounter", "KmerCounts", "KmerDHT", "KmerTable", "PackedReads", "analyze_kmers", "comm_id",
     "get_kmer_target_rank", "kmer_from_string", "kmer_to_string", "keys_to_strings", "n_longs_for",
     "synth_genome", "synth_reads", "MhmkcError", "TorchDistTransport", "MHMKC_OWNER_HASH", "MHMKC_OWNER_MINIMIZER",
-    "SharedGpuCounter",
+    "SharedGpuCounter", "assembly_stats_text",
 ]

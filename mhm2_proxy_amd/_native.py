@@ -27,6 +27,7 @@ ERRORS = {
     -6: "MHMKC_EBADCHAR",
     -7: "MHMKC_EUNSUPPORTED",
     -8: "MHMKC_ETRANSPORT",
+    -9: "MHMKC_EIO",
 }
 
 MHMKC_OWNER_HASH = 0
@@ -56,7 +57,10 @@ ABI_SYMBOLS = [
     "mhmkc_add_ctgs_device", "mhmkc_add_ctgs_from", "mhmkc_ctgs_ranks_info",
     "mhmkc_lookup_ranks", "mhmkc_lookup_ranks_device", "mhmkc_dbjg_links_ranks", "mhmkc_dbjg_links_ranks_fetch",
     "mhmkc_dbjg_links_ranks_device", "mhmkc_route_info",
+    "mhmkc_ctgs_stats_device", "mhmkc_uutigs_stats", "mhmkc_ctgs_fasta_device", "mhmkc_uutigs_fasta",
+    "mhmkc_fasta_device", "mhmkc_fasta_fetch", "mhmkc_fasta_write", "mhmkc_fasta_info",
 ]
+CTG_LEN_CLASSES = (1000, 5000, 10000, 25000, 50000)  # mhmkc_ctg_stats.len_sums (contigs.cpp:96)
 MHMKC_DEPTH_U16, MHMKC_DEPTH_F64 = 0, 1
 UUTIG_MAX_ROUNDS = 48
 URANKS_STAGES = ("gather", "build", "select")  # MHMKC_URANKS_*
@@ -136,6 +140,28 @@ class MhmkcCtgRanksInfo(C.Structure):
                                           "bytes_sent", "bytes_recv")] + \
                [(f, C.c_double) for f in ("ms_pack", "ms_move", "ms_assemble", "ms_total")] + \
                [("gathered_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class MhmkcCtgStats(C.Structure):
+    """mhmkc_ctg_stats (include/mhmkc.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("n_ctgs", "tot_len", "max_len", "n_ns")] + \
+               [("tot_depth", C.c_double), ("len_sums", C.c_uint64 * 5), ("n50", C.c_uint64), ("l50", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "len_sums"}
+        d["len_sums"] = [int(v) for v in self.len_sums]
+        return d
+
+
+class MhmkcFastaInfo(C.Structure):
+    """mhmkc_fasta_info_t (include/mhmkc.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("n_ctgs", "n_written", "n_bytes", "file_offset", "n_bytes_all", "text_bytes",
+                                          "scratch_bytes")] + \
+               [(f, C.c_double) for f in ("ms_table", "ms_copy", "ms_headers", "ms_total")] + \
+               [("write_chunks", C.c_uint64), ("ms_write", C.c_double)]
 
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -355,6 +381,14 @@ def lib() -> C.CDLL:
     L.mhmkc_dbjg_links_ranks_fetch.argtypes = [VP, VP, VP, VP]
     L.mhmkc_dbjg_links_ranks_device.argtypes = [VP, P(VP), P(VP), P(VP)]
     L.mhmkc_route_info.argtypes = [VP, P(MhmkcRouteInfo)]
+    L.mhmkc_ctgs_stats_device.argtypes = [VP, VP, VP, VP, U64, C.c_uint32, P(MhmkcCtgStats), P(MhmkcCtgStats)]
+    L.mhmkc_uutigs_stats.argtypes = [VP, C.c_uint32, P(MhmkcCtgStats), P(MhmkcCtgStats)]
+    L.mhmkc_ctgs_fasta_device.argtypes = [VP, VP, VP, VP, U64, U64, C.c_uint32, P(U64), P(U64), P(U64)]
+    L.mhmkc_uutigs_fasta.argtypes = [VP, C.c_uint32, P(U64), P(U64), P(U64)]
+    L.mhmkc_fasta_device.argtypes = [VP, P(VP), P(U64)]
+    L.mhmkc_fasta_fetch.argtypes = [VP, VP]
+    L.mhmkc_fasta_write.argtypes = [VP, C.c_char_p]
+    L.mhmkc_fasta_info.argtypes = [VP, P(MhmkcFastaInfo)]
     _lib = L
     return L
 

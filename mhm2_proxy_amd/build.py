@@ -7,6 +7,7 @@
   tools/bin/libmhmkc_handoff.so     g++: the adapter's streamed hand-off (load_ordered) timed in bench.py's process
   tools/bin/libmhmkc_qfind.so       g++: hand-off + KmerMap::find on query keys, timed in tools/query_bench.py's process
   tools/bin/libmhmkc_uhost.so       g++: hand-off + the host traversal on one thread, timed in tools/uutig_bench.py's process
+  tools/bin/libmhmkc_fhost.so       g++: fetch + the host dump_contigs / print_stats loops, timed in tools/fasta_bench.py's process
 
 Incremental: a target is rebuilt only when one of its sources is newer; libmhmkc.so also when the build id it
 carries (the SHA-256 of its sources, mhmkc_build_id) is not the tree's, whatever the file times say.
@@ -33,6 +34,7 @@ LIB_SOURCES = [CSRC / "kcount_kernels.hip", CSRC / "kcount_ctg.hip", CSRC / "kco
                CSRC / "kcount_owner.hip",
                CSRC / "kcount_query.hip", CSRC / "kcount_route.hip",
                CSRC / "kcount_uutig.hip", CSRC / "kcount_uutig_ranks.hip", CSRC / "kcount_uutig_frags.hip",
+               CSRC / "kcount_fasta.hip",
                CSRC / "fastq.hip",
                CSRC / "mhmkc_host.cpp"]
 LIB_DEPS = LIB_SOURCES + [CSRC / "kcount_launch.hpp", CSRC / "kcount_query_dev.hpp", CSRC / "kmer_ops.hpp", ROOT / "include" / "mhmkc.h"]
@@ -48,6 +50,9 @@ QFIND_DEPS = [ROOT / "tools" / "cpp" / "query_find.cpp", ROOT / "include" / "mhm
 UHOST = ROOT / "tools" / "bin" / "libmhmkc_uhost.so"
 UHOST_DEPS = [ROOT / "tools" / "cpp" / "uutig_host.cpp", ROOT / "include" / "mhmkc_dbjg.hpp",
               ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]
+# tools/fasta_bench.py's comparison route: the uutigs fetched to the host, then the adapter's host loops on one thread
+FHOST = ROOT / "tools" / "bin" / "libmhmkc_fhost.so"
+FHOST_DEPS = [ROOT / "tools" / "cpp" / "fasta_host.cpp", ROOT / "include" / "mhmkc_kcount.hpp", ROOT / "include" / "mhmkc.h"]
 # test infrastructure: the restated traversal over a given table (the multi-rank multi-k chain, tests/test_c5_scale.py)
 DBJG = ROOT / "tools" / "bin" / "libmhmkc_dbjg.so"
 DBJG_DEPS = [ROOT / "tools" / "cpp" / "dbjg_lib.cpp", ROOT / "include" / "mhmkc_dbjg.hpp",
@@ -197,6 +202,16 @@ def build_uhost(force: bool = False) -> Path:
     return UHOST
 
 
+def build_fhost(force: bool = False) -> Path:
+    if force or _stale(FHOST, FHOST_DEPS + [LIB]):
+        FHOST.parent.mkdir(parents=True, exist_ok=True)
+        tmp = FHOST.with_suffix(".tmp")
+        _run(["g++", "-O2", "-std=c++17", "-pthread", "-fPIC", "-shared", "-I", ROOT / "include", FHOST_DEPS[0], "-L",
+              PKG, "-lmhmkc", "-lz", "-Wl,-rpath,$ORIGIN/../../mhm2_proxy_amd", "-o", tmp])
+        tmp.replace(FHOST)
+    return FHOST
+
+
 def build_all(force: bool = False) -> None:
     build_lib(force)
     build_synth(force)
@@ -206,6 +221,7 @@ def build_all(force: bool = False) -> None:
     build_dbjg(force)
     build_qfind(force)
     build_uhost(force)
+    build_fhost(force)
 
 
 if __name__ == "__main__":

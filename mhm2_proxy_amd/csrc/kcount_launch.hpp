@@ -680,4 +680,43 @@ hipError_t launch_ufrag_scatter(const UfragGraph &g, int k, int me, int n_ranks,
                                 const uint64_t *offsets, uint64_t n_bases, char *seqs, const uint64_t *seg_pos,
                                 const uint64_t *recv_base, const char *recv, uint64_t recv_bytes, hipStream_t s);
 
+// Assembly statistics and FASTA text of device-resident contigs (kcount_fasta.hip). The contigs are
+// given as mhmkc_add_ctgs_device takes them (offs: n_ctgs + 1 entries). A box's bad_* fields hold ~c of the first
+// offending contig c, 0 when there is none.
+constexpr uint64_t FASTA_STATS_CHUNK = 1024;  // contigs whose depths make one partial sum, in a fixed order
+struct CtgStatsBox {
+  unsigned long long n_ctgs, tot_len, max_len, n_ns, len_sums[5];
+  unsigned long long bad_off, bad_len;  // offsets that fall or do not start at 0; a counted contig of 2^32 bases or more
+  unsigned long long n_bases;           // offs[n_ctgs]
+};
+struct FastaBox {
+  unsigned long long bad_off, bad_depth;  // a depth that is negative, -0.0, not finite or >= 2^32 (counted contigs only)
+  unsigned long long n_bases, n_written, n_bytes;
+};
+// lens [n_ctgs] (a counted contig's length, else 0), partial [ceil(n_ctgs / FASTA_STATS_CHUNK)] (the chunks' depth sums,
+// to be added in chunk order), box: zeroed here. Follows no offset into the bases.
+hipError_t launch_ctg_stats_table(const uint64_t *offs, const double *depths, uint64_t n_ctgs, uint32_t min_len,
+                                  uint32_t *lens, double *partial, CtgStatsBox *box, hipStream_t s);
+// box->n_ns += the 'N' bytes of the counted contigs; only after the table's verdict on the offsets
+hipError_t launch_ctg_stats_ns(const char *seqs, const uint64_t *offs, uint64_t n_ctgs, uint64_t n_bases, uint32_t min_len,
+                               CtgStatsBox *box, hipStream_t s);
+// N50 / L50 of the n lengths at ctg_n50_lens(scratch), of which n_counted are counted (the others are 0) and sum to
+// tot_len: out[0] = n50, out[1] = l50 (device words)
+size_t ctg_n50_scratch_bytes(uint64_t n);
+uint32_t *ctg_n50_lens(void *scratch);
+// after launch_ctg_n50: the lengths in descending order (the counted ones first)
+const uint32_t *ctg_n50_sorted(const void *scratch, uint64_t n);
+hipError_t launch_ctg_n50(uint64_t n, uint64_t n_counted, uint64_t tot_len, void *scratch, size_t scratch_bytes,
+                          unsigned long long *out, hipStream_t s);
+// the records' places: dst_off [n_ctgs + 1] in scratch, box->n_bytes = the text's length
+size_t fasta_scratch_bytes(uint64_t n_ctgs);
+hipError_t launch_fasta_table(const uint64_t *offs, const double *depths, uint64_t n_ctgs, uint64_t first_id,
+                              uint32_t min_len, void *scratch, size_t scratch_bytes, FastaBox *box, const uint64_t **dst_off,
+                              hipStream_t s);
+// the bases, then the headers, into text (16-byte aligned, whole 16-byte units allocated); only after the table's verdict
+hipError_t launch_fasta_copy(const char *seqs, const uint64_t *offs, uint64_t n_ctgs, uint64_t n_bases,
+                             const uint64_t *dst_off, uint64_t n_bytes, char *text, hipStream_t s);
+hipError_t launch_fasta_headers(const uint64_t *offs, const double *depths, uint64_t n_ctgs, uint64_t first_id,
+                                const uint64_t *dst_off, uint64_t n_bytes, char *text, hipStream_t s);
+
 }  // namespace mhm

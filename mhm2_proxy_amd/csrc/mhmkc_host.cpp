@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <condition_variable>
+#include <cerrno>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -66,6 +67,7 @@ struct DebugKnobs {
   int64_t h2d_nib = -1;       // H2D of a host batch: 1 nibbles + u32 offsets, 2 nibbles + u64 offsets, 0 the PackedRead
                               // bytes, -1 1 with >= 4 host threads, else 0
   int64_t cb0[4] = {0, 0, 0, 0};  // coarse bits by key words (0: the default)
+  int64_t fasta_chunk_bytes = 0;  // mhmkc_fasta_write: bytes per D2H copy and pwrite (0: 4 MiB)
   int64_t query_slots_log2 = 0;   // slots of the query index, as a power of two (0: the smallest one >= 2 n_out)
   // query_grid, the most workgroups of every query / uutig kernel (0: the kernels' own grids), lives where the launches
   // of kcount_query.hip and kcount_uutig.hip read it: mhm::query_grid_cap (kcount_launch.hpp)
@@ -566,6 +568,34 @@ struct mhmkc {
     d_rlinks.release();
     rlinks_ready = false;
     rinfo = mhmkc_route_info_t{};
+  }
+  // assembly statistics and FASTA text of device-resident contigs (kcount_fasta.hip). d_fa_tmp is one
+  // call's scratch; d_fasta keeps the last text (fa_bytes of it, at fa_off of a file of fa_all bytes) until the next
+  // fasta call, reset, finish or destroy (drop_fasta)
+  DevBuf d_fasta, d_fa_tmp;
+  PinBuf fa_pin;  // mhmkc_fasta_write: two chunks
+  bool fa_ready = false;
+  uint64_t fa_bytes = 0, fa_off = 0, fa_all = 0;
+  mhmkc_fasta_info_t fa_info{};
+  int ctgs_stats_local(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint32_t min_len,
+                       mhmkc_ctg_stats &m, std::vector<uint32_t> *lens_desc);
+  int ctgs_stats(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint32_t min_len,
+                 mhmkc_ctg_stats *mine, mhmkc_ctg_stats *all);
+  int n50_of(const std::vector<uint32_t> &lens, uint64_t tot, uint64_t &n50, uint64_t &l50);
+  int fasta_local(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint64_t first_id,
+                  uint32_t min_len);
+  int ctgs_fasta(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint64_t first_id,
+                 uint32_t min_len, uint64_t *n_bytes, uint64_t *file_off, uint64_t *n_all);
+  int fasta_create(const char *path);
+  int fasta_write_block(const char *path, uint64_t &chunks);
+  int fasta_write(const char *path);
+  int status_all(int lrc, const char *what);
+  void drop_fasta() {
+    d_fasta.release();
+    d_fa_tmp.release();
+    fa_ready = false;
+    fa_bytes = fa_off = fa_all = 0;
+    fa_info = mhmkc_fasta_info_t{};
   }
   void drop_query() {
     drop_uranks_scratch();
@@ -2673,6 +2703,7 @@ int mhmkc::finish(uint64_t *n_out_ret) {
   ord_ready = false;
   drop_query();
   drop_route();
+  drop_fasta();
   ctg_gathered = false;
   if ((rc = resolve_slabs())) return rc;
   hipError_t e;
@@ -3508,6 +3539,8 @@ void mhmkc_destroy(mhmkc_t h) {
   for (DevBuf *b : bufs) b->release();
   h->drop_query();
   h->drop_route();
+  h->drop_fasta();
+  h->fa_pin.release();
   DevBuf *cbufs[] = {&h->d_ctg_bytes, &h->d_ctg_offs, &h->d_ctg_win,   &h->d_ctg_depth, &h->d_ctg_scratch,
                      &h->d_ctg_state, &h->d_ctg_bucket, &h->d_ctg_done, &h->d_ctg_keys[0], &h->d_ctg_keys[1],
                      &h->d_ctg_keys[2], &h->d_ctg_keys[3]};
@@ -5684,6 +5717,434 @@ int mhmkc_uutigs_frags_info(mhmkc_t h, mhmkc_uutig_frags_info *info) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// assembly statistics and FASTA output of device-resident contigs (kcount_fasta.hip):
+// Contigs::print_stats and Contigs::dump_contigs (src/contigs.cpp:92-180)
+
+// A rank that failed alone fails every rank: with n_ranks > 1 one 8-byte all-gather, which is also a barrier
+int mhmkc::status_all(int lrc, const char *what) {
+  const int g = G();
+  if (g <= 1) return lrc;
+  const uint64_t bad = lrc ? 1 : 0;
+  std::vector<uint64_t> bads((size_t)g, 0);
+  const std::string lerr = err;
+  const int rc = allgather_host(&bad, bads.data(), 8);
+  if (lrc) {
+    err = lerr;
+    return lrc;
+  }
+  if (rc) return rc;
+  for (int r = 0; r < g; r++)
+    if (bads[(size_t)r]) return fail(MHMKC_ETRANSPORT, "%s: rank %d failed (its mhmkc_last_error says why)", what, r);
+  return MHMKC_OK;
+}
+
+// This rank's figures; lens_desc (if given): its counted lengths in descending order. d_fa_tmp: the box and the N50
+// words, the chunks' depth sums, the N50 scratch.
+int mhmkc::ctgs_stats_local(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint32_t min_len,
+                            mhmkc_ctg_stats &m, std::vector<uint32_t> *lens_desc) {
+  m = mhmkc_ctg_stats{};
+  if (lens_desc) lens_desc->clear();
+  if (!n) return MHMKC_OK;
+  if (!d_offs || !d_depths) return fail(MHMKC_EINVAL, "ctgs_stats: null pointer with n_ctgs > 0");
+  const uint64_t n_chunks = (n + mhm::FASTA_STATS_CHUNK - 1) / mhm::FASTA_STATS_CHUNK;
+  const size_t part_b = align_up(n_chunks * 8, 256), n50_b = mhm::ctg_n50_scratch_bytes(n);
+  hipError_t e = grow(d_fa_tmp, 512 + part_b + n50_b);
+  if (e != hipSuccess) return hip_fail(e, "ctgs_stats scratch");
+  char *b = d_fa_tmp.as<char>();
+  mhm::CtgStatsBox *box = (mhm::CtgStatsBox *)b;
+  unsigned long long *out = (unsigned long long *)(b + 256);
+  double *partial = (double *)(b + 512);
+  void *scratch = b + 512 + part_b;
+  mhm::CtgStatsBox hb{};
+  std::vector<double> hp((size_t)n_chunks);
+  if ((e = mhm::launch_ctg_stats_table(d_offs, d_depths, n, min_len, mhm::ctg_n50_lens(scratch), partial, box, stream)) !=
+          hipSuccess ||
+      (e = hipMemcpyAsync(&hb, box, sizeof hb, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(hp.data(), partial, n_chunks * 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess)
+    return hip_fail(e, "ctgs_stats table");
+  if (hb.bad_off)
+    return fail(MHMKC_EINVAL, "ctgs_stats: the offsets do not start at 0 or fall at contig %llu", ~hb.bad_off);
+  if (hb.bad_len) return fail(MHMKC_EUNSUPPORTED, "ctgs_stats: contig %llu has 2^32 bases or more", ~hb.bad_len);
+  if (hb.n_bases && !d_seqs) return fail(MHMKC_EINVAL, "ctgs_stats: null sequences with %llu bases", hb.n_bases);
+  // (the offsets start at 0 and never fall: every one of them is at most n_bases)
+  unsigned long long ho[2] = {0, 0};
+  mhm::CtgStatsBox hb2{};  // (the box again, for n_ns)
+  if ((e = mhm::launch_ctg_stats_ns(d_seqs, d_offs, n, hb.n_bases, min_len, box, stream)) != hipSuccess ||
+      (e = mhm::launch_ctg_n50(n, hb.n_ctgs, hb.tot_len, scratch, n50_b, out, stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&hb2, box, sizeof hb2, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(ho, out, 16, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+    return hip_fail(e, "ctgs_stats bases");
+  if (lens_desc && hb.n_ctgs) {
+    lens_desc->resize((size_t)hb.n_ctgs);
+    if ((e = hipMemcpyAsync(lens_desc->data(), mhm::ctg_n50_sorted(scratch, n), hb.n_ctgs * 4, hipMemcpyDeviceToHost,
+                            stream)) != hipSuccess)
+      return hip_fail(e, "ctgs_stats lengths");
+  }
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return hip_fail(e, "ctgs_stats");
+  m.n_ctgs = hb.n_ctgs;
+  m.tot_len = hb.tot_len;
+  m.max_len = hb.max_len;
+  m.n_ns = hb2.n_ns;
+  for (int i = 0; i < 5; i++) m.len_sums[i] = hb.len_sums[i];
+  double d = 0;
+  for (uint64_t c = 0; c < n_chunks; c++) d += hp[(size_t)c];  // the chunks in order
+  m.tot_depth = d;
+  m.n50 = ho[0];
+  m.l50 = ho[1];
+  return MHMKC_OK;
+}
+
+// N50 / L50 of host lengths (all counted), on the device
+int mhmkc::n50_of(const std::vector<uint32_t> &lens, uint64_t tot, uint64_t &n50, uint64_t &l50) {
+  n50 = l50 = 0;
+  const uint64_t n = lens.size();
+  if (!n) return MHMKC_OK;
+  const size_t n50_b = mhm::ctg_n50_scratch_bytes(n);
+  hipError_t e = grow(d_fa_tmp, 512 + n50_b);
+  if (e != hipSuccess) return hip_fail(e, "ctgs_stats scratch");
+  char *b = d_fa_tmp.as<char>();
+  unsigned long long *out = (unsigned long long *)(b + 256);
+  void *scratch = b + 512;
+  unsigned long long ho[2] = {0, 0};
+  if ((e = hipMemcpyAsync(mhm::ctg_n50_lens(scratch), lens.data(), n * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+      (e = mhm::launch_ctg_n50(n, n, tot, scratch, n50_b, out, stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(ho, out, 16, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess)
+    return hip_fail(e, "ctgs_stats N50");
+  n50 = ho[0];
+  l50 = ho[1];
+  return MHMKC_OK;
+}
+
+int mhmkc::ctgs_stats(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint32_t min_len,
+                      mhmkc_ctg_stats *mine, mhmkc_ctg_stats *all) {
+  const int g = G();
+  mhmkc_ctg_stats m{};
+  std::vector<uint32_t> lens;
+  const int lrc = ctgs_stats_local(d_seqs, d_offs, d_depths, n, min_len, m, g > 1 ? &lens : nullptr);
+  if (g <= 1) {
+    d_fa_tmp.release();
+    if (lrc) return lrc;
+    if (mine) *mine = m;
+    if (all) *all = m;
+    return MHMKC_OK;
+  }
+  // every rank's status and figures (reduce_one of contigs.cpp:144-148,162, returned on every rank)
+  enum { R_BAD, R_N, R_TOT, R_MAX, R_NS, R_CLS, R_DEPTH = R_CLS + 5, R_WORDS };
+  uint64_t rec[R_WORDS] = {lrc ? 1ull : 0ull, m.n_ctgs, m.tot_len, m.max_len, m.n_ns};
+  for (int i = 0; i < 5; i++) rec[R_CLS + i] = m.len_sums[i];
+  memcpy(&rec[R_DEPTH], &m.tot_depth, 8);
+  std::vector<uint64_t> recs((size_t)g * R_WORDS, 0);
+  const std::string lerr = err;
+  int rc = allgather_host(rec, recs.data(), 8 * R_WORDS);
+  if (lrc || rc) {
+    d_fa_tmp.release();
+    if (lrc) err = lerr;
+    return lrc ? lrc : rc;
+  }
+  mhmkc_ctg_stats a{};
+  uint64_t cmax = 0;
+  for (int r = 0; r < g; r++) {
+    const uint64_t *q = &recs[(size_t)r * R_WORDS];
+    if (q[R_BAD]) {
+      d_fa_tmp.release();
+      return fail(MHMKC_ETRANSPORT, "ctgs_stats: rank %d failed (its mhmkc_last_error says why)", r);
+    }
+    a.n_ctgs += q[R_N];
+    a.tot_len += q[R_TOT];
+    a.max_len = std::max<uint64_t>(a.max_len, q[R_MAX]);
+    a.n_ns += q[R_NS];
+    for (int i = 0; i < 5; i++) a.len_sums[i] += q[R_CLS + i];
+    double d;
+    memcpy(&d, &q[R_DEPTH], 8);
+    a.tot_depth += d;  // in rank order
+    cmax = std::max<uint64_t>(cmax, q[R_N]);
+  }
+  // the exact N50 of all ranks' contigs: every rank's counted lengths, 4 bytes each, in lists padded to the longest
+  int lrc2 = MHMKC_OK;
+  if (cmax) {
+    std::vector<uint32_t> snd((size_t)cmax, 0), rcv((size_t)cmax * g, 0), cat;
+    std::copy(lens.begin(), lens.end(), snd.begin());
+    if ((rc = allgather_host(snd.data(), rcv.data(), cmax * 4))) {
+      d_fa_tmp.release();
+      return rc;
+    }
+    cat.reserve((size_t)a.n_ctgs);
+    for (int r = 0; r < g; r++)
+      cat.insert(cat.end(), rcv.begin() + (size_t)r * cmax, rcv.begin() + (size_t)r * cmax + recs[(size_t)r * R_WORDS + R_N]);
+    lrc2 = n50_of(cat, a.tot_len, a.n50, a.l50);
+  }
+  d_fa_tmp.release();
+  if ((rc = status_all(lrc2, "ctgs_stats"))) return rc;
+  if (mine) *mine = m;
+  if (all) *all = a;
+  return MHMKC_OK;
+}
+
+// This rank's text into d_fasta. d_fa_tmp: the box, the records' lengths and places, the scan's scratch.
+int mhmkc::fasta_local(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint64_t first_id,
+                       uint32_t min_len) {
+  d_fasta.release();
+  fa_ready = false;
+  fa_bytes = fa_off = fa_all = 0;
+  fa_info = mhmkc_fasta_info_t{};
+  const uint64_t id_max = 0x7FFFFFFFFFFFFFFFull;
+  if (first_id > id_max || n > id_max - first_id)
+    return fail(MHMKC_EINVAL, "ctgs_fasta: first_id + n_ctgs exceeds 2^63 - 1 (contig %llu would be the first without an id)",
+                (unsigned long long)(first_id > id_max ? 0 : id_max - first_id));
+  fa_info.n_ctgs = n;
+  if (!n) {
+    fa_ready = true;
+    return MHMKC_OK;
+  }
+  if (!d_offs || !d_depths) return fail(MHMKC_EINVAL, "ctgs_fasta: null pointer with n_ctgs > 0");
+  const size_t sb = mhm::fasta_scratch_bytes(n);
+  hipError_t e = grow(d_fa_tmp, 512 + sb);
+  if (e != hipSuccess) return hip_fail(e, "ctgs_fasta scratch");
+  char *b = d_fa_tmp.as<char>();
+  mhm::FastaBox *box = (mhm::FastaBox *)b;
+  mhm::FastaBox hb{};
+  const uint64_t *dst_off = nullptr;
+  hipEvent_t ev[4] = {take_event(), take_event(), take_event(), take_event()};
+  auto give_back = [&] {
+    for (hipEvent_t x : ev) ev_pool.push_back(x);
+  };
+  (void)hipEventRecord(ev[0], stream);
+  if ((e = mhm::launch_fasta_table(d_offs, d_depths, n, first_id, min_len, b + 512, sb, box, &dst_off, stream)) != hipSuccess ||
+      (e = hipEventRecord(ev[1], stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(&hb, box, sizeof hb, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess) {
+    give_back();
+    return hip_fail(e, "ctgs_fasta table");
+  }
+  int rc = MHMKC_OK;
+  if (hb.bad_off)
+    rc = fail(MHMKC_EINVAL, "ctgs_fasta: the offsets do not start at 0 or fall at contig %llu", ~hb.bad_off);
+  else if (hb.bad_depth)
+    rc = fail(MHMKC_EINVAL, "ctgs_fasta: the depth of contig %llu is negative, -0.0, not finite or 2^32 or more",
+              ~hb.bad_depth);
+  else if (hb.n_bases && !d_seqs)
+    rc = fail(MHMKC_EINVAL, "ctgs_fasta: null sequences with %llu bases", hb.n_bases);
+  if (rc) {
+    give_back();
+    return rc;
+  }
+  const uint64_t nbytes = hb.n_bytes;
+  if (nbytes) {
+    // whole 16-byte units: k_fa_copy stores the last one in full
+    if ((e = d_fasta.ensure(align_up(nbytes, 16) + 16)) != hipSuccess) {
+      give_back();
+      (void)hipGetLastError();
+      return fail(MHMKC_ENOMEM, "ctgs_fasta: %llu bytes of text: %s", (unsigned long long)nbytes, hipGetErrorString(e));
+    }
+    if ((e = mhm::launch_fasta_copy(d_seqs, d_offs, n, hb.n_bases, dst_off, nbytes, d_fasta.as<char>(), stream)) !=
+            hipSuccess ||
+        (e = hipEventRecord(ev[2], stream)) != hipSuccess ||
+        (e = mhm::launch_fasta_headers(d_offs, d_depths, n, first_id, dst_off, nbytes, d_fasta.as<char>(), stream)) !=
+            hipSuccess ||
+        (e = hipEventRecord(ev[3], stream)) != hipSuccess || (e = hipStreamSynchronize(stream)) != hipSuccess) {
+      give_back();
+      d_fasta.release();
+      return hip_fail(e, "ctgs_fasta text");
+    }
+  }
+  auto ms = [&](int i, int j) {
+    float t = 0;
+    return hipEventElapsedTime(&t, ev[i], ev[j]) == hipSuccess ? (double)t : 0.0;
+  };
+  fa_info.ms_table = ms(0, 1);
+  if (nbytes) {
+    fa_info.ms_copy = ms(1, 2);
+    fa_info.ms_headers = ms(2, 3);
+    fa_info.ms_total = ms(0, 3);
+  } else {
+    fa_info.ms_total = fa_info.ms_table;
+  }
+  give_back();
+  fa_info.n_written = hb.n_written;
+  fa_info.text_bytes = d_fasta.cap;
+  fa_info.scratch_bytes = d_fa_tmp.cap;
+  fa_bytes = nbytes;
+  fa_ready = true;
+  return MHMKC_OK;
+}
+
+int mhmkc::ctgs_fasta(const char *d_seqs, const uint64_t *d_offs, const double *d_depths, uint64_t n, uint64_t first_id,
+                      uint32_t min_len, uint64_t *n_bytes, uint64_t *file_off, uint64_t *n_all) {
+  const int g = G();
+  const int lrc = fasta_local(d_seqs, d_offs, d_depths, n, first_id, min_len);
+  d_fa_tmp.release();
+  if (g <= 1) {
+    if (lrc) return lrc;
+    fa_off = 0;
+    fa_all = fa_bytes;
+  } else {
+    // dist_ofstream's prefix sum (upcxx-utils/src/ofstream.cpp:184,454) and the status, in one 16-byte all-gather
+    const uint64_t my[2] = {lrc ? 1ull : 0ull, fa_bytes};
+    std::vector<uint64_t> allv((size_t)g * 2, 0);
+    const std::string lerr = err;
+    const int rc = allgather_host(my, allv.data(), 16);
+    if (lrc || rc) {
+      drop_fasta();
+      if (lrc) err = lerr;
+      return lrc ? lrc : rc;
+    }
+    uint64_t off = 0, tot = 0;
+    for (int r = 0; r < g; r++) {
+      if (allv[(size_t)2 * r]) {
+        drop_fasta();
+        return fail(MHMKC_ETRANSPORT, "ctgs_fasta: rank %d failed (its mhmkc_last_error says why)", r);
+      }
+      if (r < cfg.rank) off += allv[(size_t)2 * r + 1];
+      tot += allv[(size_t)2 * r + 1];
+    }
+    fa_off = off;
+    fa_all = tot;
+  }
+  fa_info.n_bytes = fa_bytes;
+  fa_info.file_offset = fa_off;
+  fa_info.n_bytes_all = fa_all;
+  st.device_bytes = g_dev_live.load();
+  st.device_bytes_peak = g_dev_peak.load();
+  if (n_bytes) *n_bytes = fa_bytes;
+  if (file_off) *file_off = fa_off;
+  if (n_all) *n_all = fa_all;
+  return MHMKC_OK;
+}
+
+// The file of all ranks' texts, made, emptied and sized to fa_all (rank 0's part of dist_ofstream's open)
+int mhmkc::fasta_create(const char *path) {
+  const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (fd < 0) return fail(MHMKC_EIO, "fasta_write: cannot create %s: %s", path, strerror(errno));
+  int rc = MHMKC_OK;
+  if (ftruncate(fd, (off_t)fa_all) != 0)
+    rc = fail(MHMKC_EIO, "fasta_write: cannot set the length of %s to %llu: %s", path, (unsigned long long)fa_all,
+              strerror(errno));
+  if (close(fd) != 0 && !rc) rc = fail(MHMKC_EIO, "fasta_write: closing %s: %s", path, strerror(errno));
+  return rc;
+}
+
+// The kept text into the existing file at fa_off. Chunk c + 1 is copied into one pinned buffer while chunk c is written
+// from the other: the FASTQ file reader's scheme, the other way. A rank without bytes opens nothing.
+int mhmkc::fasta_write_block(const char *path, uint64_t &chunks) {
+  chunks = 0;
+  if (!fa_bytes) return MHMKC_OK;
+  const int fd = open(path, O_WRONLY);
+  if (fd < 0) return fail(MHMKC_EIO, "fasta_write: cannot open %s: %s", path, strerror(errno));
+  const uint64_t chunk = std::min<uint64_t>(g_dbg.fasta_chunk_bytes ? (uint64_t)g_dbg.fasta_chunk_bytes : 4ull << 20, fa_bytes);
+  const uint64_t nch = (fa_bytes + chunk - 1) / chunk;
+  hipError_t e = fa_pin.ensure(2 * chunk);
+  if (e != hipSuccess) {
+    (void)close(fd);
+    return hip_fail(e, "fasta_write staging");
+  }
+  int rc = MHMKC_OK;
+  hipEvent_t ev[2] = {take_event(), take_event()};
+  const char *text = d_fasta.as<char>();
+  auto issue = [&](uint64_t c) {
+    const uint64_t at = c * chunk, len = std::min<uint64_t>(chunk, fa_bytes - at);
+    hipError_t x = hipMemcpyAsync(fa_pin.as<char>() + (c & 1) * chunk, text + at, len, hipMemcpyDeviceToHost, stream);
+    return x != hipSuccess ? x : hipEventRecord(ev[c & 1], stream);
+  };
+  e = issue(0);
+  for (uint64_t c = 0; c < nch && e == hipSuccess && !rc; c++) {
+    if (c + 1 < nch) e = issue(c + 1);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[c & 1]);
+    if (e != hipSuccess) break;
+    const uint64_t at = c * chunk, len = std::min<uint64_t>(chunk, fa_bytes - at);
+    const char *src = fa_pin.as<char>() + (c & 1) * chunk;
+    for (uint64_t done = 0; done < len;) {
+      const ssize_t w = pwrite(fd, src + done, len - done, (off_t)(fa_off + at + done));
+      if (w < 0 && errno == EINTR) continue;
+      if (w <= 0) {
+        rc = fail(MHMKC_EIO, "fasta_write: writing %s at byte %llu: %s", path, (unsigned long long)(fa_off + at + done),
+                  w < 0 ? strerror(errno) : "nothing written");
+        break;
+      }
+      done += (uint64_t)w;
+    }
+    chunks++;
+  }
+  (void)hipStreamSynchronize(stream);  // no copy is left on its way into the staging
+  ev_pool.push_back(ev[0]);
+  ev_pool.push_back(ev[1]);
+  if (e != hipSuccess && !rc) rc = hip_fail(e, "fasta_write D2H");
+  if (close(fd) != 0 && !rc) rc = fail(MHMKC_EIO, "fasta_write: closing %s: %s", path, strerror(errno));
+  return rc;
+}
+
+int mhmkc::fasta_write(const char *path) {
+  const auto t0 = std::chrono::steady_clock::now();
+  uint64_t chunks = 0;
+  // rank 0 makes the file; with several ranks the status exchange is the barrier before anybody opens it
+  int rc = status_all(cfg.rank == 0 ? fasta_create(path) : MHMKC_OK, "fasta_write (creating the file)");
+  if (rc) return rc;
+  rc = status_all(fasta_write_block(path, chunks), "fasta_write");
+  fa_info.write_chunks = chunks;
+  fa_info.ms_write = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+int mhmkc_ctgs_stats_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const double *d_depths,
+                            uint64_t n_ctgs, uint32_t min_ctg_len, mhmkc_ctg_stats *mine, mhmkc_ctg_stats *all) {
+  if (!h) return MHMKC_EINVAL;
+  return h->ctgs_stats(d_seqs, d_seq_offsets, d_depths, n_ctgs, min_ctg_len, mine, all);
+}
+
+int mhmkc_uutigs_stats(mhmkc_t h, uint32_t min_ctg_len, mhmkc_ctg_stats *mine, mhmkc_ctg_stats *all) {
+  int rc = uutigs_need(h);
+  if (rc) return rc;
+  return h->ctgs_stats(h->u_nbases ? h->d_useq.as<char>() : nullptr, h->u_offsets(), h->u_nctgs ? h->u_depths() : nullptr,
+                       h->u_nctgs, min_ctg_len, mine, all);
+}
+
+int mhmkc_ctgs_fasta_device(mhmkc_t h, const char *d_seqs, const uint64_t *d_seq_offsets, const double *d_depths,
+                            uint64_t n_ctgs, uint64_t first_id, uint32_t min_ctg_len, uint64_t *n_bytes,
+                            uint64_t *file_offset, uint64_t *n_bytes_all) {
+  if (!h) return MHMKC_EINVAL;
+  return h->ctgs_fasta(d_seqs, d_seq_offsets, d_depths, n_ctgs, first_id, min_ctg_len, n_bytes, file_offset, n_bytes_all);
+}
+
+int mhmkc_uutigs_fasta(mhmkc_t h, uint32_t min_ctg_len, uint64_t *n_bytes, uint64_t *file_offset, uint64_t *n_bytes_all) {
+  int rc = uutigs_need(h);
+  if (rc) return rc;
+  return h->ctgs_fasta(h->u_nbases ? h->d_useq.as<char>() : nullptr, h->u_offsets(), h->u_nctgs ? h->u_depths() : nullptr,
+                       h->u_nctgs, h->cfg.n_ranks > 1 ? h->ur_first : 0, min_ctg_len, n_bytes, file_offset, n_bytes_all);
+}
+
+int mhmkc_fasta_device(mhmkc_t h, const char **d_text, uint64_t *n_bytes) {
+  if (!h) return MHMKC_EINVAL;
+  if (!h->fa_ready) return h->fail(MHMKC_ESTATE, "no FASTA text: call mhmkc_uutigs_fasta or mhmkc_ctgs_fasta_device first");
+  if (d_text) *d_text = h->fa_bytes ? h->d_fasta.as<char>() : nullptr;
+  if (n_bytes) *n_bytes = h->fa_bytes;
+  return MHMKC_OK;
+}
+
+int mhmkc_fasta_fetch(mhmkc_t h, char *text) {
+  if (!h) return MHMKC_EINVAL;
+  if (!h->fa_ready) return h->fail(MHMKC_ESTATE, "no FASTA text: call mhmkc_uutigs_fasta or mhmkc_ctgs_fasta_device first");
+  if (!h->fa_bytes) return MHMKC_OK;
+  if (!text) return h->fail(MHMKC_EINVAL, "fasta_fetch: null buffer");
+  hipError_t e = h->d2h(text, h->d_fasta.p, h->fa_bytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? MHMKC_OK : h->hip_fail(e, "fasta D2H");
+}
+
+int mhmkc_fasta_write(mhmkc_t h, const char *path) {
+  if (!h) return MHMKC_EINVAL;
+  if (!path) return h->fail(MHMKC_EINVAL, "fasta_write: null path");
+  if (!h->fa_ready) return h->fail(MHMKC_ESTATE, "no FASTA text: call mhmkc_uutigs_fasta or mhmkc_ctgs_fasta_device first");
+  return h->fasta_write(path);
+}
+
+int mhmkc_fasta_info(mhmkc_t h, mhmkc_fasta_info_t *info) {
+  if (!h || !info) return MHMKC_EINVAL;
+  *info = h->fa_info;
+  return MHMKC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // queries routed to the owner rank (kcount_route.hip): get_kmer_target_rank + rpc
 // (src/dbjg_traversal.cpp:228-236,260-274, src/kcount/kmer_dht.cpp:193-219)
 
@@ -6102,9 +6563,10 @@ int mhmkc_reset(mhmkc_t h) {
   h->n_out = 0;
   h->ord_ready = false;
   const bool had_query =
-      h->d_qidx.p || h->d_links.p || h->d_qstage.p || h->d_uctg.p || h->d_urows.p || h->d_useq.p || h->d_rlinks.p;
+      h->d_fasta.p || h->d_qidx.p || h->d_links.p || h->d_qstage.p || h->d_uctg.p || h->d_urows.p || h->d_useq.p || h->d_rlinks.p;
   h->drop_query();
   h->drop_route();
+  h->drop_fasta();
   memset(&h->st, 0, sizeof h->st);
   if (had_query || had_pc) {  // (these buffers were counted into the finished round's device_bytes: report what is left)
     h->st.device_bytes = g_dev_live.load();
@@ -6144,6 +6606,10 @@ int mhmkc_debug_set(const char *knob, int64_t value) {
   else if (k == "cb0_2") g_dbg.cb0[2] = value;
   else if (k == "cb0_3") g_dbg.cb0[3] = value;
   else if (k == "query_slots_log2") g_dbg.query_slots_log2 = value;
+  else if (k == "fasta_chunk_bytes") {
+    if (value != 0 && value < 64) return MHMKC_EINVAL;
+    g_dbg.fasta_chunk_bytes = value;
+  }
   else if (k == "query_grid") mhm::query_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else if (k == "merge_grid") mhm::merge_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));
   else if (k == "ctg_pack_grid") mhm::ctg_pack_grid_cap = (unsigned)std::max<int64_t>(0, std::min<int64_t>(value, 16384));

@@ -654,6 +654,98 @@ class KmerCounter:
         self._check(N.lib().mhmkc_uutigs_frags_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    # -- assembly statistics and FASTA output of device-resident contigs
+    def _ctg_tensors(self, seqs_t, offsets_t, depths_t):
+        import torch
+
+        n_ctgs = int(offsets_t.numel()) - 1
+        if n_ctgs < 0:
+            raise ValueError("offsets needs n_ctgs + 1 entries")
+        if int(depths_t.numel()) != n_ctgs:
+            raise ValueError("one depth per contig")
+        if seqs_t.dtype != torch.uint8 or offsets_t.dtype not in (torch.int64, torch.uint64) or \
+                depths_t.dtype != torch.float64:
+            raise TypeError("seqs_t must be uint8, offsets_t int64 or uint64, depths_t float64")
+        for t in (seqs_t, offsets_t, depths_t):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("contiguous device tensors expected")
+        self._after_torch(offsets_t)
+        return n_ctgs
+
+    def ctgs_stats_tensors(self, seqs_t, offsets_t, depths_t, min_ctg_len: int = 0) -> dict:
+        """Contigs::print_stats' figures (src/contigs.cpp:92-164) of device-resident contigs (mhmkc_ctgs_stats_device):
+        uint8 ASCII bases back to back, int64/uint64 offsets with n_ctgs + 1 entries, float64 depths. Returns {"mine": this
+        rank's, "all": over the ranks of the counter}, each a dict of n_ctgs, tot_len, max_len, n_ns, tot_depth, len_sums
+        (bases in contigs of >= 1, 5, 10, 25, 50 kbp), n50 and l50 (exact, over all ranks' contigs). Collective on a
+        counter of several ranks. The bases tensor must hold offsets_t[-1] bytes."""
+        n_ctgs = self._ctg_tensors(seqs_t, offsets_t, depths_t)
+        mine, allr = N.MhmkcCtgStats(), N.MhmkcCtgStats()
+        self._check(N.lib().mhmkc_ctgs_stats_device(self._h, seqs_t.data_ptr(), offsets_t.data_ptr(), depths_t.data_ptr(),
+                                                    n_ctgs, int(min_ctg_len), C.byref(mine), C.byref(allr)))
+        return {"mine": mine.as_dict(), "all": allr.as_dict()}
+
+    def uutigs_stats(self, min_ctg_len: int = 0) -> dict:
+        """The same of the counter's uutigs (mhmkc_uutigs_stats): ctgs.print_stats(500) of a contigging round
+        (src/contigging.cpp:152). Several ranks: after uutigs_ranks() / uutigs_frags()."""
+        mine, allr = N.MhmkcCtgStats(), N.MhmkcCtgStats()
+        self._check(N.lib().mhmkc_uutigs_stats(self._h, int(min_ctg_len), C.byref(mine), C.byref(allr)))
+        return {"mine": mine.as_dict(), "all": allr.as_dict()}
+
+    def ctgs_fasta_tensors(self, seqs_t, offsets_t, depths_t, first_id: int = 0, min_ctg_len: int = 0) -> dict:
+        """The text Contigs::dump_contigs writes (src/contigs.cpp:166-180), built and kept on the device
+        (mhmkc_ctgs_fasta_device): ">Contig<first_id + c> <depth as %f>\\n<seq>\\n" for every contig of at least min_ctg_len
+        bases. Returns {"n_bytes", "file_offset", "n_bytes_all"}; fasta_bytes(), fasta_tensor() and fasta_write() then
+        use the kept text. Collective on a counter of several ranks."""
+        n_ctgs = self._ctg_tensors(seqs_t, offsets_t, depths_t)
+        nb, fo, na = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(N.lib().mhmkc_ctgs_fasta_device(self._h, seqs_t.data_ptr(), offsets_t.data_ptr(), depths_t.data_ptr(),
+                                                    n_ctgs, int(first_id), int(min_ctg_len), C.byref(nb), C.byref(fo),
+                                                    C.byref(na)))
+        return {"n_bytes": int(nb.value), "file_offset": int(fo.value), "n_bytes_all": int(na.value)}
+
+    def uutigs_fasta(self, min_ctg_len: int = 0) -> dict:
+        """The same of the counter's uutigs, with the global ids of the ranks build (mhmkc_uutigs_fasta): the text of
+        ctgs.dump_contigs("contigs-<k>.fasta", 0) (src/contigging.cpp:147-150)."""
+        nb, fo, na = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(N.lib().mhmkc_uutigs_fasta(self._h, int(min_ctg_len), C.byref(nb), C.byref(fo), C.byref(na)))
+        return {"n_bytes": int(nb.value), "file_offset": int(fo.value), "n_bytes_all": int(na.value)}
+
+    def fasta_bytes(self) -> bytes:
+        """The kept text, copied to the host (mhmkc_fasta_fetch)."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(N.lib().mhmkc_fasta_device(self._h, C.byref(p), C.byref(n)))
+        buf = np.empty(int(n.value), dtype=np.uint8)
+        self._check(N.lib().mhmkc_fasta_fetch(self._h, buf.ctypes.data))
+        return buf.tobytes()
+
+    def fasta_tensor(self):
+        """A uint8 device tensor over the kept text (no copy; mhmkc_fasta_device), valid until the next fasta call, reset or
+        finish."""
+        import torch
+
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(N.lib().mhmkc_fasta_device(self._h, C.byref(p), C.byref(n)))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if not n.value:
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+
+        class _Text:  # (the array interface torch.as_tensor reads a foreign device pointer through)
+            __cuda_array_interface__ = {"shape": (int(n.value),), "typestr": "|u1", "data": (int(p.value), False),
+                                        "version": 2}
+
+        return torch.as_tensor(_Text(), device=dev)
+
+    def fasta_write(self, path) -> None:
+        """Write the kept text into the file at its file_offset (mhmkc_fasta_write): one rank creates and writes the file;
+        several ranks (collective) write one file together, rank 0 creating it. All ranks must see the same file."""
+        self._check(N.lib().mhmkc_fasta_write(self._h, os.fsencode(path)))
+
+    def fasta_info(self) -> dict:
+        """Contigs written, bytes, stage times (device events), memory and the last fasta_write (mhmkc_fasta_info)."""
+        info = N.MhmkcFastaInfo()
+        self._check(N.lib().mhmkc_fasta_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     # -- queries answered by the owner rank (mhmkc_lookup_ranks, mhmkc_dbjg_links_ranks)
     def lookup_ranks(self, keys, canonicalize: bool = False):
         """lookup() for k-mers that may live on any rank (mhmkc_lookup_ranks; get_kmer_target_rank + the rpc of
@@ -883,6 +975,40 @@ class SharedGpuCounter:
         if self.counter is not None:
             self.counter.close()
             self.counter = None
+
+
+
+def _ostream_double(x: float) -> str:
+    """A double as `ostream << x` prints it with the default precision: "%g" with six significant digits."""
+    return "%g" % x
+
+
+def perc_str(num: int, tot: int) -> str:
+    """upcxx_utils perc_str (upcxx-utils/src/log.cpp:428-434): "num (p%)" with p = 100 num / tot in fixed notation,
+    two decimals; 0.00 when tot is 0."""
+    return "%d (%.2f%%)" % (num, 0.0 if tot == 0 else 100.0 * num / tot)
+
+
+def assembly_stats_text(stats: dict, min_ctg_len: int) -> str:
+    """The block Contigs::print_stats logs (src/contigs.cpp:151-163), line for line, from a stats dict (uutigs_stats()
+    ["all"]): no colour codes; doubles as `ostream <<` prints them; a division by zero prints as the stream prints the
+    result (nan, -nan for 0.0 / 0 as glibc does, or inf)."""
+    def div(a: float, b: float) -> str:
+        if b == 0:
+            return "-nan" if a == 0 else ("inf" if a > 0 else "-inf")
+        return _ostream_double(a / b)
+
+    n, tot = int(stats["n_ctgs"]), int(stats["tot_len"])
+    out = ["Assembly statistics (contig lengths >= %d)" % min_ctg_len,
+           "    Number of contigs:       %d" % n,
+           "    Total assembled length:  %d" % tot,
+           "    Average contig depth:    %s" % div(float(stats["tot_depth"]), n),
+           "    Number of Ns/100kbp:     %s (%d)" % (div(float(stats["n_ns"]) * 100000.0, tot), int(stats["n_ns"])),
+           "    Max. contig length:      %d" % int(stats["max_len"]),
+           "    Contig lengths:"]
+    for kbp, s in zip((1, 5, 10, 25, 50), stats["len_sums"]):
+        out.append("        > " + ("%dkbp:" % kbp).ljust(19) + perc_str(int(s), tot))
+    return "\n".join(out) + "\n"
 
 
 def comm_id() -> bytes:
