@@ -237,6 +237,63 @@ int mhmkc_add_fastq_pairs_device(mhmkc_t h, const char *d_text, uint64_t n_bytes
 int mhmkc_add_fastq_file(mhmkc_t h, const char *path);
 int mhmkc_add_fastq_pairs_file(mhmkc_t h, const char *path);
 
+/* Read pairs given as two texts, the mates /1 in text1 and the mates /2 in text2: the reference's read library
+ * "r1.fq:r2.fq" (src/main.cpp:110-119), which FastqReader hides behind one reader that alternates between the two
+ * files (src/fastq.cpp:240-308, :509-516). The texts are read in that order, A[0], B[0], A[1], B[1], ..., until the
+ * text whose turn it is has nothing left (merge_reads' loop, src/merge_reads.cpp:318-321; fastq.cpp:518): with c1 and
+ * c2 complete records, P = min(c1, c2) pairs are merged; if c1 > P, record A[P] is checked as a record and not added
+ * (the trailing unpaired record of mhmkc_add_fastq_pairs); a text that ends inside a record is MHMKC_EINVAL only if
+ * that record's turn comes; nothing after the stop is checked. The result (PackedReads, fq_* statistics, reads, bases,
+ * the table, the error code) is what mhmkc_add_fastq_pairs gives on the interleaving of exactly the records read. No
+ * interleaved copy is made: each text gets its own line pass, one record pass pairs record p of one with record p of
+ * the other, and the merge kernels read both texts in place. Error messages name the file (1 or 2) and the 0-based
+ * record within that file, pair errors the pair. Host texts (no terminators needed). */
+int mhmkc_add_fastq_mates(mhmkc_t h, const char *text1, uint64_t n1, const char *text2, uint64_t n2);
+/* Same, with device-resident texts (only read during the call), each extending at least 4 bytes past its length as for
+ * mhmkc_add_fastq_device: any two device addresses, in either order, in one allocation or two. */
+int mhmkc_add_fastq_mates_device(mhmkc_t h, const char *d_text1, uint64_t n1, const char *d_text2, uint64_t n2);
+/* Same, from two files read in rounds (replaces the two-file FastqReader of src/fastq.cpp:240-308 and its
+ * alternating get_next_fq_record, :509-518). A round's text of each file is that file's carry (the bytes after the
+ * last pair the previous round took) plus fresh bytes up to MHMKC_FQ_BLOCK in all (environment; default 256 MB); the
+ * round takes min(n1, n2) pairs of the n1 and n2 complete records it finds, and each file carries its own remainder,
+ * so a file with shorter records simply reads less per round and no carry outgrows a block. A file without a
+ * complete record in its text gets a block more (a record longer than the block; a carry above 1 MiB without one is
+ * MHMKC_EUNSUPPORTED). The next round's bytes are read (MHMKC_FQ_THREADS preads) while the device merges, packs and
+ * extracts this round's pairs. Pinned memory: two slots of MHMKC_FQ_BLOCK + 1 MiB + 64 bytes per file, whatever the
+ * files' sizes; with the allocator's slack at most 4.5 * (MHMKC_FQ_BLOCK + 1 MiB + 64) + 4096 bytes in all
+ * (mhmkc_fastq_mates_info). The slots stay with the handle until mhmkc_destroy (about 1.16 GB at the default block,
+ * besides the two blocks mhmkc_add_fastq_file keeps); a later call with a smaller block gives the larger slots back
+ * first, so the bound holds for every call's own block. When one file is exhausted the rule above decides what of the other is still read.
+ * fq_file_blocks counts the rounds, the statistics are sums over them, mhmkc_fastq_packed holds every round's
+ * PackedReads. Errors name the round and, for each file, the byte at which that round's text starts (record and pair
+ * indices count from there); MHMKC_EINVAL if a file cannot be opened or read. A failure after the first round leaves
+ * the round partial, as for mhmkc_add_fastq_file. Every rank names its own files (the split of one file pair among
+ * ranks, set_matching_pair, src/fastq.cpp:310-396, is not provided). */
+int mhmkc_add_fastq_mates_files(mhmkc_t h, const char *path1, const char *path2);
+/* A read library named as the reference's reads_fname (FastqReader's constructor, src/fastq.cpp:250-262; main.cpp:142-148
+ * passes each name on): "a:b" is mhmkc_add_fastq_mates_files(a, b), "a:" (one unpaired file) mhmkc_add_fastq_file(a),
+ * "a" (one interleaved file) mhmkc_add_fastq_pairs_file(a). The first colon splits. An empty name or an empty first part
+ * (":b", ":") is MHMKC_EINVAL. */
+int mhmkc_add_fastq_named(mhmkc_t h, const char *name);
+
+/* What the last mhmkc_add_fastq_mates[_device|_files] call did. Every field is 8 bytes. */
+typedef struct mhmkc_fastq_mates_info {
+  uint64_t pairs;            /* pairs merged (fq_pairs) */
+  uint64_t rounds;           /* rounds (1 for the text calls; fq_file_blocks) */
+  uint64_t bytes_read_1;     /* bytes of text 1 / file 1 given to the parser (a file: bytes read from it) */
+  uint64_t bytes_read_2;
+  uint64_t bytes_used_1;     /* bytes of text 1 up to the end of its last record read */
+  uint64_t bytes_used_2;
+  uint64_t peak_carry_1;     /* files: the most bytes of file 1 carried from one round into the next */
+  uint64_t peak_carry_2;
+  uint64_t pinned_bytes;     /* files: pinned host memory the handle holds for the rounds' texts */
+  uint64_t pinned_bound;     /* files: the documented bound on it for this call's block size */
+  uint64_t block_bytes;      /* files: MHMKC_FQ_BLOCK of this call */
+  uint64_t unpaired_checked; /* 1: an unpaired record A[P] was read and checked before text 2 ran out */
+  double read_wait_s;        /* files: time the rounds waited for a read to finish after their device calls returned */
+} mhmkc_fastq_mates_info_t;
+int mhmkc_fastq_mates_info(mhmkc_t h, mhmkc_fastq_mates_info_t *info);
+
 /* The PackedReads of the last mhmkc_add_fastq[_pairs][_device] call on the device: d_bytes[n_bases] in the
  * PackedRead layout, d_offsets[n_reads + 1]. Valid until the next add_fastq, reset or destroy. Any
  * pointer may be NULL. */

@@ -1041,6 +1041,21 @@ class HashTableInserter {
     check(pairs ? mhmkc_add_fastq_pairs_file(h_, path.c_str()) : mhmkc_add_fastq_file(h_, path.c_str()), h_,
           "mhmkc_add_fastq_file");
   }
+  // two mate files (the reference's "r1.fq:r2.fq", src/fastq.cpp:240-308, :509-518), merged and counted on the device
+  // round by round without an interleaved copy
+  void add_fastq_mates_files(const std::string &path1, const std::string &path2) {
+    check(mhmkc_add_fastq_mates_files(h_, path1.c_str(), path2.c_str()), h_, "mhmkc_add_fastq_mates_files");
+  }
+  // one name of main.cpp's reads_fnames (src/main.cpp:142-148 hands each to merge_reads' FastqReader): "a:b" two mate
+  // files, "a:" one unpaired file, "a" one interleaved file (src/fastq.cpp:250-262)
+  void add_reads_fname(const std::string &reads_fname) {
+    check(mhmkc_add_fastq_named(h_, reads_fname.c_str()), h_, "mhmkc_add_fastq_named");
+  }
+  mhmkc_fastq_mates_info_t fastq_mates_info() const {
+    mhmkc_fastq_mates_info_t mi;
+    check(mhmkc_fastq_mates_info(h_, &mi), h_, "mhmkc_fastq_mates_info");
+    return mi;
+  }
   // the PackedReads of the last add_fastq, copied back (for a host that keeps them, as main.cpp does)
   void fastq_packed_reads(PackedReads &pr) const {
     uint64_t n_reads = 0, n_bases = 0;
@@ -1178,6 +1193,10 @@ class KmerDHT {
   void add_packed_reads(const PackedReads &pr) { ht_inserter.add_packed_reads(pr); }
   void add_fastq(const std::string &text) { ht_inserter.add_fastq(text); }
   void add_fastq_file(const std::string &path, bool pairs = false) { ht_inserter.add_fastq_file(path, pairs); }
+  void add_fastq_mates_files(const std::string &path1, const std::string &path2) {
+    ht_inserter.add_fastq_mates_files(path1, path2);
+  }
+  void add_reads_fname(const std::string &reads_fname) { ht_inserter.add_reads_fname(reads_fname); }
   void flush_updates() { ht_inserter.flush_inserts(); }
   template <int PREV_MAX_K>
   void add_ctgs_from(KmerDHT<PREV_MAX_K> &prev) {

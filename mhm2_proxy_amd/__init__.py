@@ -20,6 +20,7 @@ from .kcount import (  # noqa: F401
     kmer_to_string,
     keys_to_strings,
     n_longs_for,
+    split_reads_fname,
     synth_genome,
     synth_reads,
 )
@@ -29,5 +30,5 @@ __all__ = [
     "KmerCounter", "KmerCounts", "KmerDHT", "KmerTable", "PackedReads", "analyze_kmers", "comm_id",
     "get_kmer_target_rank", "kmer_from_string", "kmer_to_string", "keys_to_strings", "n_longs_for",
     "synth_genome", "synth_reads", "MhmkcError", "TorchDistTransport", "MHMKC_OWNER_HASH", "MHMKC_OWNER_MINIMIZER",
-    "SharedGpuCounter", "assembly_stats_text",
+    "SharedGpuCounter", "assembly_stats_text", "split_reads_fname",
 ]

@@ -59,6 +59,8 @@ ABI_SYMBOLS = [
     "mhmkc_dbjg_links_ranks_device", "mhmkc_route_info",
     "mhmkc_ctgs_stats_device", "mhmkc_uutigs_stats", "mhmkc_ctgs_fasta_device", "mhmkc_uutigs_fasta",
     "mhmkc_fasta_device", "mhmkc_fasta_fetch", "mhmkc_fasta_write", "mhmkc_fasta_info",
+    "mhmkc_add_fastq_mates", "mhmkc_add_fastq_mates_device", "mhmkc_add_fastq_mates_files", "mhmkc_add_fastq_named",
+    "mhmkc_fastq_mates_info",
 ]
 CTG_LEN_CLASSES = (1000, 5000, 10000, 25000, 50000)  # mhmkc_ctg_stats.len_sums (contigs.cpp:96)
 MHMKC_DEPTH_U16, MHMKC_DEPTH_F64 = 0, 1
@@ -162,6 +164,17 @@ class MhmkcFastaInfo(C.Structure):
                                           "scratch_bytes")] + \
                [(f, C.c_double) for f in ("ms_table", "ms_copy", "ms_headers", "ms_total")] + \
                [("write_chunks", C.c_uint64), ("ms_write", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class MhmkcFastqMatesInfo(C.Structure):
+    """mhmkc_fastq_mates_info_t (include/mhmkc.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("pairs", "rounds", "bytes_read_1", "bytes_read_2", "bytes_used_1",
+                                          "bytes_used_2", "peak_carry_1", "peak_carry_2", "pinned_bytes",
+                                          "pinned_bound", "block_bytes", "unpaired_checked")] + \
+               [("read_wait_s", C.c_double)]
 
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -332,6 +345,11 @@ def lib() -> C.CDLL:
     L.mhmkc_add_fastq_pairs_device.argtypes = [VP, VP, U64]
     L.mhmkc_add_fastq_file.argtypes = [VP, C.c_char_p]
     L.mhmkc_add_fastq_pairs_file.argtypes = [VP, C.c_char_p]
+    L.mhmkc_add_fastq_mates.argtypes = [VP, C.c_char_p, U64, C.c_char_p, U64]
+    L.mhmkc_add_fastq_mates_device.argtypes = [VP, VP, U64, VP, U64]
+    L.mhmkc_add_fastq_mates_files.argtypes = [VP, C.c_char_p, C.c_char_p]
+    L.mhmkc_add_fastq_named.argtypes = [VP, C.c_char_p]
+    L.mhmkc_fastq_mates_info.argtypes = [VP, P(MhmkcFastqMatesInfo)]
     L.mhmkc_fastq_packed.argtypes = [VP, P(VP), P(VP), P(U64), P(U64)]
     L.mhmkc_fastq_fetch.argtypes = [VP, VP, VP]
     L.mhmkc_finish.argtypes = [VP, P(U64)]

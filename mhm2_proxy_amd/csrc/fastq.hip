@@ -472,6 +472,7 @@ __host__ __device__ inline uint32_t *long_pairs(void *desc_buf, uint64_t n_pairs
 // name to compare); then the pair's names (replace_spaces: spaces read as '_', four characters per load) and
 // pair numbers are checked (:320-321) and its descriptor written. A trailing unpaired record (odd count) is
 // checked as a record only.
+// (fq_mate_check, below, restates these checks on line words its caller has loaded: a change here belongs there too.)
 __device__ bool fq_record_check(const char *text, uint64_t n, const unsigned long long *line_end, uint64_t r,
                                 unsigned long long *len, unsigned long long *err, FqRec &o, uint64_t &pb, uint64_t &pe,
                                 char &last) {
@@ -1151,6 +1152,143 @@ hipError_t launch_offs_rebase(unsigned long long *dst, const unsigned long long 
   if (!n) return hipSuccess;
   const uint64_t blocks = std::min<uint64_t>(4096, (n + 255) / 256);
   k_offs_rebase<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(dst, src, n, delta);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Read pairs from two texts: A holds the mates /1, B the mates /2, record p of A pairs with record p of B (the
+// reference's FastqReader for "r1.fq:r2.fq" alternates between the two files, src/fastq.cpp:509-516). Each text has
+// its own line words (k_fq_count / k_fq_lines run once per text). k_fq_mate_records is k_fq_pair_records for that
+// layout: one lane per pair, the records' checks, the name and /1 /2 tests, the long-pair list and the descriptor;
+// lengths and errors are written at the interleaved record indices 2p and 2p + 1, so that the offset scan, the
+// quality scratch, k_fq_merge and k_fq_merge_pack run unchanged on the result. The merge kernels address all lines
+// from one base pointer: the lower of the two texts' addresses (base), with offs_a / offs_b the texts' distances
+// from it (one of them 0), added to the descriptor's offsets here. No byte of text moves.
+namespace {
+
+// fq_record_check on line words the caller has already loaded (lw[i]: the word ending line 4r + i - 1 of this text),
+// reporting at record ri (the record's index in the alternating order). The loads are the caller's so that both
+// mates' words are requested before either record's dependent id-line loads begin.
+__device__ bool fq_mate_check(const char *text, uint64_t n, const uint64_t (&lw)[5], uint64_t r, uint64_t ri,
+                              unsigned long long *len, unsigned long long *err, FqRec &o, uint64_t &pb, uint64_t &pe,
+                              char &last) {
+  uint64_t lb[4], le[4], te[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    lb[i] = (4 * r + i) ? (lw[i] & FQ_LE_MASK) + 1 : 0;
+    le[i] = lw[i + 1] & FQ_LE_MASK;
+    te[i] = le[i] == n ? rtrim_end(text, lb[i], le[i]) : le[i] - ((lw[i + 1] >> FQ_LE_BITS) & 0xffffu);
+  }
+  len[ri] = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    if (le[i] - lb[i] > FQ_MAX_LINE) {
+      fq_fail(err, ri, FQ_E_LONG);
+      return false;
+    }
+  const unsigned char c_id = r ? (unsigned char)(lw[0] >> 56) : (n ? (unsigned char)text[0] : 0);
+  const unsigned char c_plus = (unsigned char)(lw[2] >> 56);
+  if (te[0] == lb[0] || c_id != '@') {
+    fq_fail(err, ri, FQ_E_ID);
+    return false;
+  }
+  if (le[2] == lb[2] || c_plus != '+') {
+    fq_fail(err, ri, FQ_E_PLUS);
+    return false;
+  }
+  if (!fq_norm(text, lb[0], te[0], pb, pe, last)) {
+    fq_fail(err, ri, FQ_E_NAME);
+    return false;
+  }
+  const uint64_t L = te[1] - lb[1];
+  if (L != te[3] - lb[3]) {
+    fq_fail(err, ri, FQ_E_LEN);
+    return false;
+  }
+  len[ri] = L;
+  o.idb = lb[0];
+  o.idte = te[0];
+  o.sb = lb[1];
+  o.qb = lb[3];
+  o.L = (uint32_t)L;
+  return true;
+}
+
+// n_pairs pairs; extra: A's record n_pairs exists, is read before B runs out and is checked as a record only (the
+// trailing unpaired record of k_fq_pair_records). len has 2 n_pairs + extra + 1 elements.
+__global__ __launch_bounds__(FQ_THREADS) void k_fq_mate_records(const char *text_a, uint64_t n_a,
+                                                                 const unsigned long long *line_a, const char *text_b,
+                                                                 uint64_t n_b, const unsigned long long *line_b,
+                                                                 uint64_t n_pairs, uint32_t extra, uint64_t offs_a,
+                                                                 uint64_t offs_b, unsigned long long *len,
+                                                                 unsigned long long *err, PairDesc *desc,
+                                                                 uint32_t *long_list) {
+  const uint64_t p = (uint64_t)blockIdx.x * FQ_THREADS + threadIdx.x;
+  if (p > n_pairs) return;
+  const bool tail = p == n_pairs;
+  if (tail && !extra) {  // the scan's last element: offs[2 n_pairs] = total
+    len[2 * n_pairs] = 0;
+    return;
+  }
+  // both texts' line words first: ten independent loads in flight before the first one is used
+  uint64_t wa[5], wb[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++) wa[i] = (4 * p + i) ? line_a[4 * p + i - 1] : 0;
+#pragma unroll
+  for (int i = 0; i < 5; i++) wb[i] = (!tail && (4 * p + i)) ? line_b[4 * p + i - 1] : 0;
+  FqRec a, b;
+  uint64_t pb1 = 0, pe1 = 0, pb2 = 0, pe2 = 0;
+  char l1 = 0, l2 = 0;
+  const bool ok1 = fq_mate_check(text_a, n_a, wa, p, 2 * p, len, err, a, pb1, pe1, l1);
+  if (tail) {  // the unpaired A record; the scan's last element
+    len[2 * n_pairs + 1] = 0;
+    return;
+  }
+  const bool ok2 = fq_mate_check(text_b, n_b, wb, p, 2 * p + 1, len, err, b, pb2, pe2, l2);
+  PairDesc d{0, 0, 0, 0, ~0u, 0};
+  if (ok1 && ok2) {
+    bool same = pe1 - pb1 == pe2 - pb2;
+    for (uint64_t i = 0; same && i < pe1 - pb1; i += 4) {  // replace_spaces: a space reads as '_'
+      const uint64_t left = pe1 - pb1 - i;
+      const uint32_t valid = left >= 4 ? ~0u : (1u << (8 * left)) - 1;
+      uint32_t x = load4(text_a + pb1, (uint32_t)i), y = load4(text_b + pb2, (uint32_t)i);
+      const uint32_t sx = (zero_bytes(x ^ 0x20202020u) >> 7) * 0xffu, sy = (zero_bytes(y ^ 0x20202020u) >> 7) * 0xffu;
+      x = (x & ~sx) | (0x5f5f5f5fu & sx);
+      y = (y & ~sy) | (0x5f5f5f5fu & sy);
+      same = ((x ^ y) & valid) == 0;
+    }
+    if (!same) {
+      fq_fail(err, 2 * p + 1, FQ_E_PAIR_NAME);
+    } else if (l1 != '1' || l2 != '2') {
+      fq_fail(err, 2 * p + 1, FQ_E_PAIR_NUM);
+    } else {
+      d = PairDesc{offs_a + a.sb, offs_a + a.qb, offs_b + b.sb, offs_b + b.qb, a.L, b.L};
+      if (a.L > MG_LONG || b.L > MG_LONG) long_list[16 + atomicAdd(long_list, 1u)] = (uint32_t)p;
+    }
+  }
+  desc[p] = d;
+}
+
+}  // namespace
+
+const char *fq_mates_base(const char *text_a, const char *text_b, uint64_t *offs_a, uint64_t *offs_b) {
+  const char *base = (uintptr_t)text_b < (uintptr_t)text_a ? text_b : text_a;
+  *offs_a = (uint64_t)((uintptr_t)text_a - (uintptr_t)base);
+  *offs_b = (uint64_t)((uintptr_t)text_b - (uintptr_t)base);
+  return base;
+}
+
+hipError_t launch_fq_mate_records(const char *text_a, uint64_t n_a, const unsigned long long *line_a, const char *text_b,
+                                  uint64_t n_b, const unsigned long long *line_b, uint64_t n_pairs, bool extra,
+                                  unsigned long long *len, unsigned long long *err, void *desc_buf, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(long_pairs(desc_buf, n_pairs), 0, 4, s);
+  if (e != hipSuccess) return e;
+  uint64_t offs_a = 0, offs_b = 0;
+  (void)fq_mates_base(text_a, text_b, &offs_a, &offs_b);
+  const uint64_t nt = n_pairs + 1;
+  k_fq_mate_records<<<dim3((unsigned)((nt + FQ_THREADS - 1) / FQ_THREADS)), dim3(FQ_THREADS), 0, s>>>(
+      text_a, n_a, line_a, text_b, n_b, line_b, n_pairs, extra ? 1u : 0u, offs_a, offs_b, len, err, (PairDesc *)desc_buf,
+      long_pairs(desc_buf, n_pairs));
   return hipGetLastError();
 }
 

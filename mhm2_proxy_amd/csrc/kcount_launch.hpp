@@ -432,6 +432,14 @@ hipError_t launch_fq_merge_pack(const char *text, const void *desc_buf, uint64_t
 hipError_t launch_fq_pack(const char *text, const unsigned long long *line_end, uint64_t n_rec,
                           const unsigned long long *offs, int qual_offset, uint8_t *out, unsigned long long *err,
                           hipStream_t s);
+// read pairs from two texts (A: mates /1, B: mates /2, each with its own line words): launch_fq_pair_records for
+// that layout. len and err use the alternating order's record indices (A's record p is 2p, B's 2p + 1); extra: A's
+// record n_pairs is checked as a record only (len has 2 n_pairs + extra + 1 elements). The descriptors' offsets are
+// relative to fq_mates_base, the text pointer to give launch_fq_merge / launch_fq_merge_pack.
+const char *fq_mates_base(const char *text_a, const char *text_b, uint64_t *offs_a, uint64_t *offs_b);
+hipError_t launch_fq_mate_records(const char *text_a, uint64_t n_a, const unsigned long long *line_a, const char *text_b,
+                                  uint64_t n_b, const unsigned long long *line_b, uint64_t n_pairs, bool extra,
+                                  unsigned long long *len, unsigned long long *err, void *desc_buf, hipStream_t s);
 
 // Output hand-off to the reference's owner rank (kcount_owner.hip): get_kmer_target_rank =
 // minimizer_hash_fast(minimizer_len) % rank_n (src/kcount/kmer_dht.cpp:193-196, src/kmer.cpp:344-393,454-463).

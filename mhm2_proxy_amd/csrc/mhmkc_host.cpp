@@ -641,6 +641,20 @@ struct mhmkc {
   // complete records (pairs) are parsed and *consumed is the length of their text
   int add_fastq(const char *d_text, uint64_t n, bool pairs = false, uint64_t *consumed = nullptr);
   PinBuf fq_file_buf;  // mhmkc_add_fastq_file: two blocks (one read while the other is copied; pinned)
+  // Read pairs from two texts (mhmkc_add_fastq_mates*): text A holds the mates /1, B the mates /2. A text that is not
+  // final is a block of a longer file: only its complete records count and it never ends "inside a record". The round
+  // takes P = min(records of A, records of B) pairs; it is done when the text whose turn comes next (A[P], then B[P])
+  // is final and has nothing left. on_cut runs as soon as the bytes used of each text are known (before the record
+  // pass, the merge and the extraction are enqueued), so that the file reader can start on the next round's data.
+  struct FqMatesRound {
+    uint64_t pairs = 0, recs[2] = {0, 0}, used[2] = {0, 0};
+    bool done = false, extra = false;  // extra: A[P] was read (and checked) before B ran out
+  };
+  DevBuf d_fq_chunk_b, d_fq_lines_b;  // text B's chunk counts and line words (A's are d_fq_chunk, d_fq_lines)
+  int add_fastq_mates(const char *d_a, uint64_t n_a, bool final_a, const char *d_b, uint64_t n_b, bool final_b,
+                      FqMatesRound &rd, const std::function<void(const FqMatesRound &)> &on_cut = nullptr);
+  PinBuf fq_mates_buf;  // mhmkc_add_fastq_mates_files: two slots per file (pinned)
+  mhmkc_fastq_mates_info_t fq_mi{};
   // contig pass (add_ctg_kmers): contigs in the PackedRead byte layout, kept on the host until finish
   std::vector<uint8_t> ctg_bytes;
   std::vector<uint64_t> ctg_offs{0}, ctg_win{0};  // byte offsets, counted-window prefix
@@ -3550,6 +3564,7 @@ void mhmkc_destroy(mhmkc_t h) {
   h->x_send.release();
   h->x_recv.release();
   h->fq_file_buf.release();
+  h->fq_mates_buf.release();
   for (auto &p : h->prof) {
     h->ev_pool.push_back(p.a);
     h->ev_pool.push_back(p.b);
@@ -3994,6 +4009,464 @@ int mhmkc_add_fastq_pairs_file(mhmkc_t h, const char *path) { return add_fastq_f
 
 int mhmkc_add_fastq_pairs(mhmkc_t h, const char *text, uint64_t n_bytes) {
   return add_fastq_host(h, text, n_bytes, true);
+}
+
+// Read pairs from two texts on the device (fastq.hip: k_fq_mate_records) -> PackedReads -> add_view. The line pass runs
+// once per text; from the record pass on, the launches are add_fastq's paired ones, on lengths, offsets and
+// descriptors laid out as the alternating order's (A's record p is record 2p, B's 2p + 1).
+int mhmkc::add_fastq_mates(const char *d_a, uint64_t n_a, bool final_a, const char *d_b, uint64_t n_b, bool final_b,
+                           FqMatesRound &rd, const std::function<void(const FqMatesRound &)> &on_cut) {
+  int rc = begin_round();
+  if (rc) return rc;
+  rd = FqMatesRound{};
+  fq_reads = fq_bases = 0;
+  st.fq_pairs = st.fq_merged = st.fq_ambiguous = st.fq_overlap_bases = 0;
+  if (n_a > mhm::FQ_LE_MASK || n_b > mhm::FQ_LE_MASK)
+    return fail(MHMKC_EINVAL, "FASTQ text larger than 2^40 bytes in one call");
+  if ((rc = resolve_slabs())) return rc;
+  hipError_t e;
+  const char *txt[2] = {d_a, d_b};
+  const uint64_t n[2] = {n_a, n_b};
+  const bool fin[2] = {final_a, final_b};
+  DevBuf *chunk_buf[2] = {&d_fq_chunk, &d_fq_chunk_b}, *line_buf[2] = {&d_fq_lines, &d_fq_lines_b};
+  uint64_t nch[2];
+  unsigned long long *cbase[2] = {nullptr, nullptr};
+  size_t tmp_bytes = 0;
+  for (int t = 0; t < 2; t++) {
+    nch[t] = (n[t] + mhm::FQ_CHUNK - 1) / mhm::FQ_CHUNK;
+    tmp_bytes = std::max(tmp_bytes, mhm::fq_scan_tmp_bytes(nch[t] + 1));
+    if ((e = grow(*chunk_buf[t], (nch[t] + 1) * 16)) != hipSuccess) return hip_fail(e, "fastq chunk counts");
+  }
+  if ((e = grow(d_fq_tmp, tmp_bytes)) != hipSuccess) return hip_fail(e, "fastq scan scratch");
+  unsigned long long newlines[2] = {0, 0};
+  char last[2] = {'\n', '\n'};
+  prof_begin(MHMKC_STAGE_OTHER);
+  e = hipSuccess;
+  for (int t = 0; t < 2 && e == hipSuccess; t++) {
+    if (!n[t]) continue;
+    unsigned long long *cnt = chunk_buf[t]->as<unsigned long long>();
+    cbase[t] = cnt + nch[t] + 1;
+    e = hipMemsetAsync(cnt + nch[t], 0, 8, stream);
+    if (e == hipSuccess) e = mhm::launch_fq_count(txt[t], n[t], cnt, stream);
+    if (e == hipSuccess) e = mhm::fq_scan(d_fq_tmp.p, tmp_bytes, cnt, cbase[t], nch[t] + 1, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&newlines[t], cbase[t] + nch[t], 8, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&last[t], txt[t] + n[t] - 1, 1, hipMemcpyDeviceToHost, stream);
+  }
+  prof_end();
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "fastq newline count");
+  // a final text's last line may lack its newline (fgets returns it); a block's continues in the next round
+  uint64_t all_lines[2], c[2];
+  bool trunc[2];
+  for (int t = 0; t < 2; t++) {
+    all_lines[t] = newlines[t] + (fin[t] && n[t] && last[t] != '\n' ? 1 : 0);
+    c[t] = all_lines[t] / 4;
+    trunc[t] = fin[t] && all_lines[t] % 4;
+    rd.recs[t] = c[t];
+  }
+  const uint64_t P = std::min(c[0], c[1]);
+  // after P pairs it is A's turn, then B's: the reads stop when the text whose turn it is has nothing left
+  unsigned long long trunc_err = ~0ull;
+  if (c[0] > P) {  // A[P] is there; B has no record P
+    if (fin[1]) {
+      rd.done = rd.extra = true;
+      if (trunc[1]) trunc_err = ((unsigned long long)(2 * P + 1) << 4) | mhm::FQ_E_TRUNC;
+    }
+  } else if (fin[0]) {
+    rd.done = true;
+    if (trunc[0]) trunc_err = ((unsigned long long)(2 * P) << 4) | mhm::FQ_E_TRUNC;
+  }
+  rd.pairs = P;
+  const uint64_t take[2] = {P + (rd.extra ? 1 : 0), P};  // records of each text this round reads
+  unsigned long long *lend[2] = {nullptr, nullptr};
+  unsigned long long n_end[2] = {n_a, n_b}, cut[2] = {0, 0};
+  for (int t = 0; t < 2; t++) {
+    if ((e = grow(*line_buf[t], std::max<uint64_t>(all_lines[t], 1) * 8)) != hipSuccess) return hip_fail(e, "fastq lines");
+    lend[t] = line_buf[t]->as<unsigned long long>();
+  }
+  prof_begin(MHMKC_STAGE_OTHER);
+  for (int t = 0; t < 2 && e == hipSuccess; t++) {
+    if (!n[t]) continue;
+    e = mhm::launch_fq_lines(txt[t], n[t], cbase[t], lend[t], stream);
+    if (e == hipSuccess && all_lines[t] > newlines[t])
+      e = hipMemcpyAsync(lend[t] + all_lines[t] - 1, &n_end[t], 8, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && take[t])
+      e = hipMemcpyAsync(&cut[t], lend[t] + 4 * take[t] - 1, 8, hipMemcpyDeviceToHost, stream);
+  }
+  prof_end();
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hip_fail(e, "fastq lines");
+  for (int t = 0; t < 2; t++) rd.used[t] = take[t] ? std::min<uint64_t>(n[t], (uint64_t)(cut[t] & mhm::FQ_LE_MASK) + 1) : 0;
+  if (on_cut) on_cut(rd);
+  const uint64_t R = take[0] + take[1];  // records in the alternating order
+  unsigned long long first_err = trunc_err, n_bases = 0;
+  if (R) {
+    if ((e = grow(d_fq_len, (R + 1) * 8)) != hipSuccess || (e = grow(d_fq_offs, (R + 1) * 8)) != hipSuccess ||
+        (e = grow(d_fq_err, 8)) != hipSuccess || (e = grow(d_fq_desc, mhm::fq_pair_desc_bytes(P))) != hipSuccess)
+      return hip_fail(e, "fastq records");
+    const size_t tmp2 = mhm::fq_scan_tmp_bytes(R + 1);
+    if (tmp2 > tmp_bytes) {
+      if ((e = grow(d_fq_tmp, tmp2)) != hipSuccess) return hip_fail(e, "fastq scan scratch");
+      tmp_bytes = tmp2;
+    }
+    unsigned long long *len = d_fq_len.as<unsigned long long>(), *offs = d_fq_offs.as<unsigned long long>();
+    unsigned long long *err_d = d_fq_err.as<unsigned long long>();
+    uint64_t oa = 0, ob = 0;
+    const char *base = mhm::fq_mates_base(d_a, d_b, &oa, &ob);
+    prof_begin(MHMKC_STAGE_OTHER);
+    e = hipMemsetAsync(err_d, 0xff, 8, stream);
+    if (e == hipSuccess)
+      e = mhm::launch_fq_mate_records(d_a, n_a, lend[0], d_b, n_b, lend[1], P, rd.extra, len, err_d, d_fq_desc.p, stream);
+    if (e == hipSuccess) e = mhm::fq_scan(d_fq_tmp.p, tmp_bytes, len, offs, R + 1, stream);
+    prof_end();
+    if (e != hipSuccess) return hip_fail(e, "fastq records");
+    if ((e = hipMemcpyAsync(&n_bases, offs + R, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream)) != hipSuccess)
+      return hip_fail(e, "fastq records D2H");
+    // merge_reads, as add_fastq: the record offsets lay out the quality scratch, the verdicts give the output lengths
+    if ((e = grow(d_fq_recoffs, (R + 1) * 8)) != hipSuccess ||
+        (e = grow(d_fq_scratch, std::max<uint64_t>(n_bases, 1) + 64)) != hipSuccess ||
+        (e = grow(d_fq_pairinfo, (P + 1) * 4)) != hipSuccess || (e = grow(d_fq_stats, 128)) != hipSuccess ||
+        (e = grow(d_fq_len, (2 * P + 1) * 8)) != hipSuccess)
+      return hip_fail(e, "fastq pairs");
+    const size_t tmp3 = mhm::fq_scan_tmp_bytes(2 * P + 1);
+    if (tmp3 > tmp_bytes) {
+      if ((e = grow(d_fq_tmp, tmp3)) != hipSuccess) return hip_fail(e, "fastq scan scratch");
+      tmp_bytes = tmp3;
+    }
+    unsigned long long *roffs = d_fq_recoffs.as<unsigned long long>(), *fst = d_fq_stats.as<unsigned long long>();
+    prof_begin(MHMKC_STAGE_OTHER);
+    e = hipMemcpyAsync(roffs, offs, (R + 1) * 8, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(fst, 0, 128, stream);
+    if (e == hipSuccess)
+      e = mhm::launch_fq_merge(base, n_a, lend[0], P, roffs, cfg.qual_offset, d_fq_scratch.as<char>(), d_fq_desc.p,
+                               d_fq_pairinfo.as<uint32_t>(), len, err_d, fst, stream);
+    if (e == hipSuccess) e = mhm::fq_scan(d_fq_tmp.p, tmp_bytes, len, offs, 2 * P + 1, stream);
+    prof_end();
+    if (e != hipSuccess) return hip_fail(e, "fastq merge");
+    unsigned long long hs[4] = {0, 0, 0, 0};
+    if ((e = hipMemcpyAsync(&n_bases, offs + 2 * P, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(hs, fst, 32, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(stream)) != hipSuccess)
+      return hip_fail(e, "fastq merge D2H");
+    st.fq_pairs = P;
+    st.fq_merged = hs[1];
+    st.fq_ambiguous = hs[2];
+    st.fq_overlap_bases = hs[3];
+    if ((e = grow(d_fq_bytes, std::max<uint64_t>(n_bases, 1) + 64)) != hipSuccess) return hip_fail(e, "fastq bytes");
+    prof_begin(MHMKC_STAGE_OTHER);
+    e = mhm::launch_fq_merge_pack(base, d_fq_desc.p, P, roffs, d_fq_scratch.as<char>(), d_fq_pairinfo.as<uint32_t>(), offs,
+                                  cfg.qual_offset, d_fq_bytes.as<uint8_t>(), err_d, stream);
+    prof_end();
+    unsigned long long dev_err = ~0ull;
+    if (e == hipSuccess) e = hipMemcpyAsync(&dev_err, err_d, 8, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, "fastq pack");
+    first_err = std::min(first_err, dev_err);
+  }
+  if (first_err != ~0ull) {
+    // the alternating order's record ri is record ri / 2 of file 1 + (ri & 1); the pair kinds are reported at the
+    // pair's second record
+    const unsigned long long ri = first_err >> 4, rec = ri >> 1;
+    const int file = 1 + (int)(ri & 1);
+    switch ((int)(first_err & 15)) {
+      case mhm::FQ_E_PAIR_NAME:
+        return fail(MHMKC_EINVAL, "FASTQ pair %llu (file 1 record %llu, file 2 record %llu): mismatched pair names", rec,
+                    rec, rec);
+      case mhm::FQ_E_PAIR_NUM:
+        return fail(MHMKC_EINVAL,
+                    "FASTQ pair %llu (file 1 record %llu, file 2 record %llu): mismatched pair numbers (not /1, /2)", rec,
+                    rec, rec);
+      case mhm::FQ_E_CHAR2: return fail(MHMKC_EBADCHAR, "FASTQ file 2 record %llu: illegal base character", rec);
+      case mhm::FQ_E_QUAL:
+        return fail(MHMKC_EINVAL, "FASTQ pair %llu (file 1 record %llu, file 2 record %llu): invalid quality score in the "
+                                  "overlap", rec, rec, rec);
+      case mhm::FQ_E_CHAR1: return fail(MHMKC_EBADCHAR, "FASTQ file 1 record %llu: illegal base character", rec);
+      case mhm::FQ_E_ID:
+        return fail(MHMKC_EINVAL, "invalid FASTQ file %d record %llu: expected read name (@)", file, rec);
+      case mhm::FQ_E_PLUS: return fail(MHMKC_EINVAL, "invalid FASTQ file %d record %llu: expected '+'", file, rec);
+      case mhm::FQ_E_NAME:
+        return fail(MHMKC_EINVAL, "invalid FASTQ file %d record %llu: incorrect name format", file, rec);
+      case mhm::FQ_E_LEN:
+        return fail(MHMKC_EINVAL, "invalid FASTQ file %d record %llu: sequence length != quals length", file, rec);
+      case mhm::FQ_E_LONG:
+        return fail(MHMKC_EUNSUPPORTED, "FASTQ file %d record %llu: line longer than %llu characters", file, rec,
+                    (unsigned long long)mhm::FQ_MAX_LINE);
+      case mhm::FQ_E_CHAR: return fail(MHMKC_EBADCHAR, "FASTQ file %d record %llu: illegal base character", file, rec);
+      default: return fail(MHMKC_EINVAL, "FASTQ file %d ends inside record %llu", file, rec);
+    }
+  }
+  const uint64_t R_out = 2 * P;
+  fq_reads = R_out;
+  fq_bases = n_bases;
+  st.reads += R_out;
+  st.bases += n_bases;
+  if (R_out == 0) return MHMKC_OK;
+  qcut_pending = cfg.qual_cutoff;
+  mhm::ReadsView rv{d_fq_bytes.as<uint8_t>(), d_fq_offs.as<uint64_t>(), R_out, n_bases, 0, 0, 0};
+  return add_view(rv, 0, false);
+}
+
+static void fq_mates_info_text(mhmkc_t h, const mhmkc::FqMatesRound &rd, uint64_t n1, uint64_t n2) {
+  mhmkc_fastq_mates_info_t &mi = h->fq_mi;
+  mi = mhmkc_fastq_mates_info_t{};
+  mi.pairs = h->st.fq_pairs;
+  mi.rounds = 1;
+  mi.bytes_read_1 = n1, mi.bytes_read_2 = n2;
+  mi.bytes_used_1 = rd.used[0], mi.bytes_used_2 = rd.used[1];
+  mi.unpaired_checked = rd.extra ? 1 : 0;
+}
+
+int mhmkc_add_fastq_mates_device(mhmkc_t h, const char *d_text1, uint64_t n1, const char *d_text2, uint64_t n2) {
+  if (!h) return MHMKC_EINVAL;
+  if ((n1 && !d_text1) || (n2 && !d_text2)) return h->fail(MHMKC_EINVAL, "null device buffer");
+  mhmkc::FqMatesRound rd;
+  const int rc = h->add_fastq_mates(d_text1, n1, true, d_text2, n2, true, rd);
+  fq_mates_info_text(h, rd, n1, n2);
+  return rc;
+}
+
+// where text 2 starts in the staging buffer that holds both texts (text 1 at 0, its padding, then an aligned start)
+static uint64_t fq_mates_second(uint64_t n1) { return align_up(n1 + 16, 256); }
+
+int mhmkc_add_fastq_mates(mhmkc_t h, const char *text1, uint64_t n1, const char *text2, uint64_t n2) {
+  if (!h) return MHMKC_EINVAL;
+  if ((n1 && !text1) || (n2 && !text2)) return h->fail(MHMKC_EINVAL, "null host buffer");
+  int rc = h->resolve_slabs();  // an earlier add_fastq's text may still be read
+  if (rc) return rc;
+  hipError_t e;
+  const uint64_t o2 = fq_mates_second(n1);
+  if ((e = h->grow(h->d_fq_text, o2 + n2 + 16)) != hipSuccess) return h->hip_fail(e, "fastq staging");
+  char *d = h->d_fq_text.as<char>();
+  if ((n1 && (e = hipMemcpyAsync(d, text1, n1, hipMemcpyHostToDevice, h->stream)) != hipSuccess) ||
+      (n2 && (e = hipMemcpyAsync(d + o2, text2, n2, hipMemcpyHostToDevice, h->stream)) != hipSuccess))
+    return h->hip_fail(e, "fastq H2D");
+  mhmkc::FqMatesRound rd;
+  rc = h->add_fastq_mates(d, n1, true, d + o2, n2, true, rd);
+  fq_mates_info_text(h, rd, n1, n2);
+  if (rc == MHMKC_OK && (e = hipStreamSynchronize(h->stream)) != hipSuccess) return h->hip_fail(e, "add_fastq_mates");
+  return rc;
+}
+
+// Two mate files in rounds (include/mhmkc.h). Per file two pinned slots of FQ_CARRY + block + 64 bytes: round i's text
+// of a file is in slot i & 1, the carry first, the fresh bytes after it. As soon as round i knows how many bytes of each
+// text its pairs use (on_cut: after the line pass, before the record pass, the merge, the pack and the extraction), a
+// reader thread copies each file's remainder to the front of the other slot and preads fresh bytes after it: as many as
+// bring the text back to `block` bytes, none if the carry alone is that long, a whole block if the text held no
+// complete record. So a text is at most max(block, carry + block) bytes with carry <= FQ_CARRY in the second case, and
+// the file with the shorter records reads less per round instead of carrying more.
+static int add_fastq_mates_files(mhmkc_t h, const char *path1, const char *path2) {
+  if (!h) return MHMKC_EINVAL;
+  if (!path1 || !path2) return h->fail(MHMKC_EINVAL, "null path");
+  const char *path[2] = {path1, path2};
+  int fd[2] = {-1, -1};
+  uint64_t size[2] = {0, 0};
+  auto close_all = [&] {
+    for (int f = 0; f < 2; f++)
+      if (fd[f] >= 0) close(fd[f]);
+  };
+  for (int f = 0; f < 2; f++) {
+    struct stat sb;
+    fd[f] = open(path[f], O_RDONLY);
+    if (fd[f] < 0 || fstat(fd[f], &sb) != 0) {
+      close_all();
+      return h->fail(MHMKC_EINVAL, "cannot open FASTQ file %d %s", f + 1, path[f]);
+    }
+    size[f] = (uint64_t)sb.st_size;
+  }
+  uint64_t block = 256ull << 20;
+  if (const char *env = getenv("MHMKC_FQ_BLOCK")) block = std::max<uint64_t>(64, strtoull(env, nullptr, 10));
+  int nthr = 8;
+  if (const char *env = getenv("MHMKC_FQ_THREADS")) nthr = std::max(1, std::min(64, atoi(env)));
+  const uint64_t slot = FQ_CARRY + block + 64;
+  mhmkc_fastq_mates_info_t mi{};
+  mi.block_bytes = block;
+  mi.pinned_bound = 4 * slot + 4 * slot / 8 + 4096;  // PinBuf's slack on four slots
+  hipError_t e;
+  // slots left by a call with a larger block are given back first: the bound is this call's, not the handle's history's
+  if (h->fq_mates_buf.cap > mi.pinned_bound) h->fq_mates_buf.release();
+  if ((e = h->fq_mates_buf.ensure(4 * slot)) != hipSuccess) {
+    close_all();
+    return h->hip_fail(e, "fastq mate file slots");
+  }
+  mi.pinned_bytes = h->fq_mates_buf.cap;
+  char *buf[2][2];
+  for (int f = 0; f < 2; f++)
+    for (int s = 0; s < 2; s++) buf[f][s] = h->fq_mates_buf.as<char>() + (2 * f + s) * slot;
+  const uint64_t fail_round = g_dbg.fq_read_fail >= 0 ? (uint64_t)g_dbg.fq_read_fail : ~0ull;
+  // file f's bytes [off, off + len) into dst, in parallel pieces
+  auto read_span = [&](int f, uint64_t off, uint64_t len, char *dst) -> bool {
+    if (!len) return true;
+    const int T = (int)std::min<uint64_t>((uint64_t)nthr, (len + 65535) / 65536);
+    const uint64_t piece = (len + T - 1) / T;
+    std::vector<std::thread> th;
+    std::vector<char> ok(T, 1);
+    auto part = [&, f, off, dst](int t, uint64_t a, uint64_t b) {
+      for (uint64_t p = a; p < b;) {
+        const ssize_t r = pread(fd[f], dst + p, (size_t)(b - p), (off_t)(off + p));
+        if (r <= 0) {
+          ok[t] = 0;
+          return;
+        }
+        p += (uint64_t)r;
+      }
+    };
+    for (int t = 1; t < T; t++) {
+      const uint64_t a = std::min(len, t * piece), b = std::min(len, a + piece);
+      if (a < b) th.emplace_back(part, t, a, b);
+    }
+    part(0, 0, std::min(len, piece));
+    for (auto &x : th) x.join();
+    for (char v : ok)
+      if (!v) return false;
+    return true;
+  };
+  uint64_t a_reads = 0, a_bases = 0;
+  auto keep_grow = [&](DevBuf &b, size_t used, size_t need) -> hipError_t {  // (as add_fastq_file's)
+    if (need <= b.cap && b.p) return hipSuccess;
+    hipError_t ge = hipStreamSynchronize(h->stream);
+    if (ge != hipSuccess) return ge;
+    DevBuf nb;
+    if ((ge = nb.ensure(std::max(need, 2 * b.cap))) != hipSuccess) return ge;
+    if (used && b.p && (ge = hipMemcpy(nb.p, b.p, std::min(used, b.cap), hipMemcpyDeviceToDevice)) != hipSuccess) {
+      nb.release();
+      return ge;
+    }
+    b.release();
+    b = nb;
+    return hipSuccess;
+  };
+  int rc = MHMKC_OK;
+  bool added = false;
+  uint64_t acc[4] = {0, 0, 0, 0}, rounds = 0;
+  uint64_t n[2], pos[2];  // the round's text length and the file bytes read so far, per file
+  for (int f = 0; f < 2 && rc == MHMKC_OK; f++) {
+    n[f] = pos[f] = std::min(block, size[f]);
+    if (fail_round == 0 || !read_span(f, 0, n[f], buf[f][0]))
+      rc = h->fail(MHMKC_EINVAL, "read error in FASTQ file %d %s", f + 1, path[f]);
+  }
+  for (uint64_t i = 0; rc == MHMKC_OK; i++) {
+    const int s = (int)(i & 1);
+    const bool fin[2] = {pos[0] == size[0], pos[1] == size[1]};
+    uint64_t carry[2] = {0, 0}, got[2] = {0, 0};
+    int read_bad = 0;  // the file (1, 2) whose read failed; 3: a record longer than the carry limit
+    std::thread reader;
+    auto on_cut = [&](const mhmkc::FqMatesRound &rd) {
+      if (rd.done) return;
+      for (int f = 0; f < 2; f++) {
+        carry[f] = n[f] - rd.used[f];
+        const uint64_t left = size[f] - pos[f];
+        got[f] = rd.recs[f] == 0 ? std::min(block, left) : carry[f] < block ? std::min(block - carry[f], left) : 0;
+        if (rd.recs[f] == 0 && carry[f] > FQ_CARRY) read_bad = 3;
+      }
+      if (read_bad) return;
+      reader = std::thread([&, i, s] {
+        for (int f = 0; f < 2; f++) {
+          memcpy(buf[f][s ^ 1], buf[f][s] + (n[f] - carry[f]), carry[f]);
+          if (i + 1 == fail_round || !read_span(f, pos[f], got[f], buf[f][s ^ 1] + carry[f])) {
+            read_bad = f + 1;
+            return;
+          }
+        }
+      });
+    };
+    mhmkc::FqMatesRound rd;
+    if ((rc = h->resolve_slabs()) == MHMKC_OK) {  // the previous round's texts may still be read by its extraction
+      const uint64_t o2 = fq_mates_second(n[0]);
+      char *d = nullptr;
+      if ((e = h->grow(h->d_fq_text, o2 + n[1] + 16)) != hipSuccess ||
+          (d = h->d_fq_text.as<char>(), false) ||
+          (n[0] && (e = hipMemcpyAsync(d, buf[0][s], n[0], hipMemcpyHostToDevice, h->stream)) != hipSuccess) ||
+          (n[1] && (e = hipMemcpyAsync(d + o2, buf[1][s], n[1], hipMemcpyHostToDevice, h->stream)) != hipSuccess))
+        rc = h->hip_fail(e, "fastq mates H2D");
+      else
+        rc = h->add_fastq_mates(d, n[0], fin[0], d + o2, n[1], fin[1], rd, on_cut);
+      if (rc == MHMKC_OK) added = true;
+    }
+    const auto t_wait = std::chrono::steady_clock::now();
+    if (reader.joinable()) reader.join();
+    mi.read_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count();
+    if (rc) {  // locate the bad record: the parser numbers records and pairs from the start of this round's texts
+      char where[200];
+      snprintf(where, sizeof where, " (FASTQ mate files round %llu, whose texts start at file 1 byte %llu and file 2 byte %llu)",
+               (unsigned long long)i, (unsigned long long)(pos[0] - n[0]), (unsigned long long)(pos[1] - n[1]));
+      h->err += where;
+      break;
+    }
+    rounds++;
+    mi.bytes_used_1 += rd.used[0], mi.bytes_used_2 += rd.used[1];
+    if (rd.extra) mi.unpaired_checked = 1;
+    if (h->fq_reads) {
+      const uint64_t r = h->fq_reads, nb = h->fq_bases;
+      if ((e = keep_grow(h->d_fqa_bytes, a_bases, a_bases + nb + 64)) != hipSuccess ||
+          (e = keep_grow(h->d_fqa_offs, (a_reads + 1) * 8, (a_reads + r + 1) * 8)) != hipSuccess ||
+          (a_reads == 0 && (e = hipMemsetAsync(h->d_fqa_offs.p, 0, 8, h->stream)) != hipSuccess) ||
+          (nb && (e = hipMemcpyAsync(h->d_fqa_bytes.as<char>() + a_bases, h->d_fq_bytes.p, nb, hipMemcpyDeviceToDevice,
+                                     h->stream)) != hipSuccess) ||
+          (e = mhm::launch_offs_rebase(h->d_fqa_offs.as<unsigned long long>() + a_reads + 1,
+                                       h->d_fq_offs.as<unsigned long long>() + 1, r, a_bases, h->stream)) != hipSuccess) {
+        rc = h->hip_fail(e, "fastq mate files packed reads");
+        break;
+      }
+      a_reads += r;
+      a_bases += nb;
+    }
+    acc[0] += h->st.fq_pairs, acc[1] += h->st.fq_merged, acc[2] += h->st.fq_ambiguous, acc[3] += h->st.fq_overlap_bases;
+    if (rd.done) break;
+    if (read_bad == 3) {
+      rc = h->fail(MHMKC_EUNSUPPORTED, "FASTQ record longer than %llu bytes", (unsigned long long)FQ_CARRY);
+      break;
+    }
+    if (read_bad) {
+      rc = h->fail(MHMKC_EINVAL, "read error in FASTQ file %d %s", read_bad, path[read_bad - 1]);
+      break;
+    }
+    for (int f = 0; f < 2; f++) {
+      n[f] = carry[f] + got[f];
+      pos[f] += got[f];
+    }
+    mi.peak_carry_1 = std::max<uint64_t>(mi.peak_carry_1, carry[0]);
+    mi.peak_carry_2 = std::max<uint64_t>(mi.peak_carry_2, carry[1]);
+  }
+  close_all();
+  if (rc && added) h->partial = true;
+  if (rc == MHMKC_OK) {  // mhmkc_fastq_packed / mhmkc_fastq_fetch now see every round's PackedReads
+    if (a_reads == 0 && ((e = keep_grow(h->d_fqa_offs, 0, 8)) != hipSuccess ||
+                         (e = hipMemsetAsync(h->d_fqa_offs.p, 0, 8, h->stream)) != hipSuccess))
+      rc = h->hip_fail(e, "fastq mate files packed reads");
+    std::swap(h->d_fq_bytes, h->d_fqa_bytes);  // (the last round's extraction may still read the old buffer:
+    std::swap(h->d_fq_offs, h->d_fqa_offs);    //  both stay allocated)
+    h->fq_reads = a_reads;
+    h->fq_bases = a_bases;
+  }
+  h->st.fq_pairs = acc[0], h->st.fq_merged = acc[1], h->st.fq_ambiguous = acc[2], h->st.fq_overlap_bases = acc[3];
+  h->st.fq_file_blocks = rounds;
+  mi.pairs = acc[0];
+  mi.rounds = rounds;
+  mi.bytes_read_1 = pos[0], mi.bytes_read_2 = pos[1];
+  h->fq_mi = mi;
+  return rc;
+}
+
+int mhmkc_add_fastq_mates_files(mhmkc_t h, const char *path1, const char *path2) {
+  return add_fastq_mates_files(h, path1, path2);
+}
+
+int mhmkc_add_fastq_named(mhmkc_t h, const char *name) {
+  if (!h) return MHMKC_EINVAL;
+  if (!name || !*name) return h->fail(MHMKC_EINVAL, "empty reads file name");
+  const char *colon = strchr(name, ':');  // the first colon splits (fastq.cpp:250)
+  if (!colon) return mhmkc_add_fastq_pairs_file(h, name);  // one interleaved file
+  const std::string a(name, (size_t)(colon - name)), b(colon + 1);
+  if (a.empty()) return h->fail(MHMKC_EINVAL, "reads file name '%s': no first file before the colon", name);
+  if (b.empty()) return mhmkc_add_fastq_file(h, a.c_str());  // "a:": one unpaired file
+  return add_fastq_mates_files(h, a.c_str(), b.c_str());
+}
+
+int mhmkc_fastq_mates_info(mhmkc_t h, mhmkc_fastq_mates_info_t *info) {
+  if (!h || !info) return MHMKC_EINVAL;
+  *info = h->fq_mi;
+  return MHMKC_OK;
 }
 
 int mhmkc_fastq_packed(mhmkc_t h, const uint8_t **d_bytes, const uint64_t **d_offsets, uint64_t *n_reads,

@@ -33,6 +33,18 @@ def n_longs_for(k: int) -> int:
     return k // 32 + 1
 
 
+def split_reads_fname(name: str) -> tuple:
+    """A read library's name as FastqReader's constructor reads it (src/fastq.cpp:250-262; the first colon splits):
+    "a:b" -> ("mates", a, b), two mate files; "a:" -> ("single", a, None), one unpaired file; "a" ->
+    ("interleaved", a, None). What mhmkc_add_fastq_named does with each. An empty first part raises ValueError."""
+    a, colon, b = str(name).partition(":")
+    if not a:
+        raise ValueError(f"reads file name {name!r}: no first file")
+    if not colon:
+        return ("interleaved", a, None)
+    return ("mates", a, b) if b else ("single", a, None)
+
+
 # ------------------------------------------------------------------------------------------------
 # Kmer helpers (2-bit MSB-first longs, src/kmer.cpp:178-188)
 
@@ -346,6 +358,50 @@ class KmerCounter:
         self._after_torch(text_t)
         fn = N.lib().mhmkc_add_fastq_pairs_device if pairs else N.lib().mhmkc_add_fastq_device
         self._check(fn(self._h, text_t.data_ptr(), n))
+
+    def add_fastq_mates(self, text1, text2) -> None:
+        """Read pairs as two FASTQ texts, the mates /1 in text1 and the mates /2 in text2 (the reference's library
+        "r1.fq:r2.fq", src/main.cpp:110-119, which FastqReader alternates between, src/fastq.cpp:509-518): the
+        result of add_fastq_pairs on the interleaving of the records read, without making that interleaving."""
+        b1 = text1.encode("ascii") if isinstance(text1, str) else bytes(text1)
+        b2 = text2.encode("ascii") if isinstance(text2, str) else bytes(text2)
+        self._check(N.lib().mhmkc_add_fastq_mates(self._h, b1, len(b1), b2, len(b2)))
+
+    def add_fastq_mates_tensors(self, t1, t2, n1: int | None = None, n2: int | None = None) -> None:
+        """add_fastq_mates on texts already in HBM (uint8 torch tensors on the counter's device, anywhere in memory,
+        in either order). Each buffer must extend 4 bytes past its text (pass n <= numel - 4 to use a tensor as is;
+        otherwise that text is copied into a padded buffer first)."""
+        import torch
+
+        ts, ns = [], []
+        for t, n in ((t1, n1), (t2, n2)):
+            n = int(t.numel()) if n is None else int(n)
+            if int(t.numel()) < n + 4:
+                padded = torch.zeros(n + 16, dtype=torch.uint8, device=t.device)
+                padded[:n].copy_(t.reshape(-1)[:n])
+                t = padded
+            ts.append(t)
+            ns.append(n)
+        self._fq_text = ts  # keep them alive while the call runs
+        self._after_torch(ts[0])
+        self._check(N.lib().mhmkc_add_fastq_mates_device(self._h, ts[0].data_ptr(), ns[0], ts[1].data_ptr(), ns[1]))
+
+    def add_fastq_mates_files(self, path1, path2) -> None:
+        """Two mate files read in rounds of MHMKC_FQ_BLOCK bytes per file (mhmkc_add_fastq_mates_files): each round
+        merges the pairs both texts hold complete and every file carries its own remainder; the next round's bytes
+        are read while the device works. fastq_packed() then holds the PackedReads of all rounds."""
+        self._check(N.lib().mhmkc_add_fastq_mates_files(self._h, os.fsencode(str(path1)), os.fsencode(str(path2))))
+
+    def add_fastq_named(self, name) -> None:
+        """A read library named as the reference's reads_fname (split_reads_fname): "a:b" two mate files, "a:" one
+        unpaired file, "a" one interleaved file."""
+        self._check(N.lib().mhmkc_add_fastq_named(self._h, os.fsencode(str(name))))
+
+    def fastq_mates_info(self) -> dict:
+        """mhmkc_fastq_mates_info of the last add_fastq_mates* call."""
+        info = N.MhmkcFastqMatesInfo()
+        self._check(N.lib().mhmkc_fastq_mates_info(self._h, C.byref(info)))
+        return info.as_dict()
 
     def fastq_packed(self) -> tuple[np.ndarray, np.ndarray]:
         """The PackedReads (bytes, offsets) of the last add_fastq call, copied to the host."""
